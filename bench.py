@@ -13,6 +13,15 @@ Rank 0 prints TWO JSON lines: the full record (every probe's object; also writte
 gpurun_out/bench_full_n<N>.json) and, LAST, the compact contract line (tools/bench_line.py: the contract's keys, the
 `roofline` and `cpu_baseline` objects and one number per secondary leg; never more than 6 KB - round 5's single 20 KB
 line could not be parsed by the driver).
+
+A plain run (`bench.py --gpus 1 --steps K --warmup W`) does only what the headline needs: set-up, W warm-up views, the K
+timed views, and the two lines above - its record holds the headline, the roofline of the timed region's field-kernel
+launches and the committed PMC figures for these kernel sources.  Every other measurement (the other view loop, the CPU
+baseline with its parity check, the training probes, the renders off the tuned configuration, the trained scene and, for
+N > 1, the collective legs) runs only with `--full`, after the headline, as before.  `--dump-outputs DIR` writes what
+the timed loop returned for its last view (every per-ray output of Trainer.render_sequence) as DIR/<name>.npy, float32
+(float64 for integer outputs), at most 64 MB; the inputs depend on the arguments only, so two builds can be compared
+output for output.
 """
 import argparse
 import json
@@ -150,6 +159,12 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--res", type=int, default=800)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every secondary measurement as well (the other view loop, CPU baseline "
+                         "and parity, training probes, other configurations, trained scene; N > 1: the collective legs); "
+                         "the --no-* switches below select among them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the per-ray outputs of the last timed view as DIR/<name>.npy (float32 / float64, <= 64 MB)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-train-probe", action="store_true")
     ap.add_argument("--train-steps", type=int, default=100,
@@ -242,13 +257,18 @@ def main():
             r = get_rays(poses_d[view:view + 1], intr, H, W)
             yield {"rays_o": r["rays_o"], "rays_d": r["rays_d"], "H": H, "W": W}
 
-    def render_views(first, n, pipeline):
-        """-> (sample counters of the n views, the last view's frame [H,W,3])"""
-        cs, frame = [], None
+    last_out = {}
+
+    def render_views(first, n, pipeline, keep_last=False):
+        """-> (sample counters of the n views, the last view's frame [H,W,3]); keep_last: the last view's whole output
+        dict is also left in last_out["out"] (--dump-outputs)"""
+        cs, frame, out = [], None, None
         for _, out in viewer.render_sequence(views(first, n), pipeline=pipeline):
             # samples the field actually evaluated (the early-terminating mode may evaluate fewer than were marched)
             cs.append(out["num_evaluated"] if "num_evaluated" in out else out["num_samples"])
             frame = out["image"]
+        if keep_last:
+            last_out["out"] = out
         return cs, frame.view(H, W, 3)
 
     def step(i):                                   # one view, one stream (CPU baseline / parity leg)
@@ -279,13 +299,17 @@ def main():
     if sclk is not None:
         sclk.start()
     t0 = time.perf_counter()
-    counters, _ = render_views(args.warmup, args.steps, bool(args.pipeline))
+    counters, _ = render_views(args.warmup, args.steps, bool(args.pipeline), keep_last=bool(args.dump_outputs))
     barrier()
     elapsed = time.perf_counter() - t0
     clocks = sclk.stop() if sclk is not None else None
     gc.enable()
     if clocks is not None:
         clocks["xcd_map"] = xcd_map_probe()
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_out["out"])
+    last_out.clear()
 
     n_samples = int(sum(int(c[0]) for c in counters))
     kernel_ms = sum(a.elapsed_time(b) for a, b, _ in ev_pairs)
@@ -365,7 +389,7 @@ def main():
                               "what": "samples x 1024 B over the wall clock of the timed loop, per GPU"}
         line["loop"] = ("Trainer.render_sequence, FramePipeline (two alternating streams; field kernels serialised)"
                         if args.pipeline else "Trainer.render_sequence, one view at a time on one stream")
-        if not args.no_pipeline_probe:
+        if args.full and not args.no_pipeline_probe:
             # the same frames through the OTHER loop, after the headline's timed region
             try:
                 other = not args.pipeline
@@ -392,16 +416,16 @@ def main():
                                              "achieved_alone": round(alone, 1), "avg_launch_ms_alone": round(kms, 4)})
             except Exception as e:                            # noqa: BLE001
                 line["pipelined" if not args.pipeline else "one_stream"] = {"error": f"{type(e).__name__}: {e}"[:300]}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line["cpu_baseline"], line["parity"] = cpu_baseline(room, net, step(0)["frame"],
                                                                     render_view0=lambda: step(0)["frame"])
             except Exception as e:                            # noqa: BLE001
                 line["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"[:300]}
     del net
-    if world > 1:
+    if args.full and world > 1:
         secondary_multi(args, line, dev, rank, world, backend, red_dev, t_start)
-    elif not args.no_train_probe:
+    elif args.full and not args.no_train_probe:
         secondary_single(args, line, dev, red_dev)
     if rank == 0:
         line["bench_wall_s"] = round(time.perf_counter() - t_start, 1)
@@ -409,6 +433,30 @@ def main():
     if world > 1:
         dist.barrier()             # the ranks leave together (rank 0 alone ran the single-GPU legs after the probes)
         dist.destroy_process_group()
+
+
+DUMP_LIMIT_BYTES = 64 * 1000 * 1000
+
+
+def dump_outputs(path, out):
+    """--dump-outputs: every tensor of the last timed view's output dict -> path/<key>.npy, float32 (float64 for integer
+    outputs, exact for sample counters).  Over DUMP_LIMIT_BYTES in all (large --res) the per-ray outputs are cut to the same
+    fixed, seeded sample of rays, in ray order."""
+    torch.cuda.synchronize()
+    arrs = {}
+    for k, v in out.items():
+        if not torch.is_tensor(v):
+            continue
+        v = v.detach()
+        arrs[k] = (v.float() if v.is_floating_point() or v.dtype == torch.bool else v.double()).cpu().numpy()
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES:
+        n_rays = max(a.shape[1] for a in arrs.values() if a.ndim >= 2)
+        keep = np.sort(np.random.default_rng(0).choice(n_rays, int(n_rays * DUMP_LIMIT_BYTES / total * 0.95), replace=False))
+        arrs = {k: (a[:, keep] if a.ndim >= 2 and a.shape[1] == n_rays else a) for k, a in arrs.items()}
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrs.items():
+        np.save(os.path.join(path, f"{k}.npy"), np.ascontiguousarray(a))
 
 
 def _try(line, key, fn):

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Everything the committed profiles/ artefacts of a round come from, in one GPU call:
-#   GPU test suite, the default bench line, the same command under rocprofv3 --kernel-trace --stats, the PMC passes
+#   GPU test suite, the bench's --full record, the same command under rocprofv3 --kernel-trace --stats, the PMC passes
 #   over the render loop (-> traffic json keyed by the kernel sources' sha), the PMC passes over the scatter of the
 #   instance-stage training step, and kernel statistics of both training steps.
 # usage (GPU box, repo root): bash tools/refresh_profiles.sh <tag>      results under gpurun_out/<tag>/
@@ -25,10 +25,10 @@ bash tools/pmc_bound.sh ${TAG}_pmcb > $O/bound_pmc.txt 2>&1; cp gpurun_out/${TAG
 # round 6: MFMA pipe utilisation of the field kernel and of the head-backward kernels (the `mfma` pass of the three PMC runs above)
 python tools/mfma_json.py gpurun_out/${TAG}_pmc gpurun_out/${TAG}_pmct gpurun_out/${TAG}_pmcn $O/r06_mfma.json > /dev/null; echo "mfma json rc=$?"
 cp $O/r06_traffic.json $O/r06_scatter_requests.json $O/r06_bound_traffic.json $O/r06_mfma.json $R/profiles/
-python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cp gpurun_out/bench_full_n1.json $O/bench_full_n1.json
+python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; cp $O/../bench_full_n1.json $O/bench_full_n1.json
 export TMPDIR=/tmp
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python3 $R/bench.py --steps 20 --warmup 3 \
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -o bench -- python3 $R/bench.py --full --steps 20 --warmup 3 \
   > $O/bench_profiled.json 2> $O/bench_profiled.err; echo "profiled bench rc=$?"
 timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace_inst -o inst -- python3 $R/tools/train_probe.py 40 \
   > $O/train_probe.txt 2>&1

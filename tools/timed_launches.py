@@ -1,4 +1,4 @@
-"""The headline kernel's launches in the kernel trace of the profiled default bench command, beside the launch times
+"""The headline kernel's launches in the kernel trace of the profiled `bench.py --full` command, beside the launch times
 bench.py measured with HIP events in the same run (profiles/r0Xz_bench_timed_launches.txt).
 Sequence of fused frame-kernel launches in bench.py: W warm-up + K timed frames of the pipelined loop (the headline's
 timed region -> roofline.frac / avg_launch_ms), then 4 warm-up + min(K, 60) timed frames of the one-stream loop
