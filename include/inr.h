@@ -36,8 +36,9 @@ extern "C" {
 
 /* Bumped whenever an existing prototype changes or an entry point is removed (round 2 changed four argument lists
  * without a bump: a stale library or an external caller built against the old header was only rejected by accident).
- * instance_nerf_amd/_lib.py refuses a library whose version differs from the one it was written against. */
-#define INR_ABI_VERSION 9
+ * instance_nerf_amd/_lib.py refuses a library whose version differs from the one it was written against.
+ * 10: inr_instance_lattice, inr_instance_volume_stats. */
+#define INR_ABI_VERSION 10
 #define INR_MAX_LEVELS 16
 
 enum {
@@ -517,6 +518,31 @@ int inr_instance_forward(const float* x, int64_t M, const int32_t* n_samples_dev
                          const float* embeddings, const inr_grid_desc* desc /*host*/,
                          const float* packed /*device*/, int32_t K, float* logits /*[M,K]*/,
                          inr_stream_t s);
+/* 3-D instance masks of a trained instance field (the field's own segmentation, in the voxel layout NeRF-RCNN's masks use).
+ * One launch over the [W, L, H] lattice of inr_nerf_forward_lattice (same axes, same walk, coordinates clamped to
+ * [-bound, bound]): the NeRF's density logit (gather + the two sigma-net layers; nerf_packed = inr_nerf_pack_weights'
+ * buffer) gives sigma = exp(logit) * density_scale, and a voxel is occupied when sigma >= sigma_thresh.  Runs of 16
+ * voxels along W without an occupied voxel skip the instance field; elsewhere the instance MLP (inst_packed =
+ * inr_instance_pack_weights' buffer for K_pad = 16 * ceil(K / 16) rows, K = 1..64 real channels) is reduced on chip:
+ *   labels     uint8 [W, L, H]: arg-max over channels 0..K-1 (lowest channel on ties), 255 = unoccupied;
+ *   confidence float [W, L, H]: max-softmax over the K channels, 0 where unoccupied (4-byte aligned);
+ *   density_logit float [W, L, H] (nullable, 4-byte aligned): the raw density logit of every voxel.
+ * Padded channels K..K_pad-1 never win.  Tables below 2 GiB each; sigma_thresh / density_scale not NaN.             */
+int inr_instance_lattice(const float* ax_w, const float* ax_l, const float* ax_h, int32_t W, int32_t L, int32_t H,
+                         float bound, const float* nerf_embeddings, const inr_grid_desc* nerf_desc /*host*/,
+                         const float* nerf_packed /*device*/, float density_scale, float sigma_thresh,
+                         const float* inst_embeddings, const inr_grid_desc* inst_desc /*host*/,
+                         const float* inst_packed /*device*/, int32_t K, uint8_t* labels, float* confidence,
+                         float* density_logit, inr_stream_t s);
+/* Per-channel statistics of such a label volume (labels uint8 [W, L, H], values >= K ignored): counts int32 [K],
+ * boxes int32 [K, 6] = inclusive voxel-index bounds (min iw, il, ih, max iw, il, ih; all -1 for an empty channel),
+ * conf_sum float [K] = sum of the channel's confidences.  Bit-reproducible: per-workgroup partials in fixed slots of
+ * `workspace` (device, >= INR_INSTANCE_STATS_WORKSPACE_BYTES, 4-byte aligned) and a fixed-order final pass, no float
+ * atomics.  Two launches on `s`.                                                                                    */
+#define INR_INSTANCE_STATS_WORKSPACE_BYTES (512 * 64 * 8 * 4)
+int inr_instance_volume_stats(const uint8_t* labels, const float* confidence, int32_t W, int32_t L, int32_t H, int32_t K,
+                              void* workspace, int64_t workspace_bytes, int32_t* counts, int32_t* boxes, float* conf_sum,
+                              inr_stream_t s);
 
 /* ---- 3-D RoIAlign ("next" row f2; replaces roi_align.roi_align.roi_align_3d, the one FFI call in the
  * reference tree: /root/reference/nerf_rcnn/model/utils.py:604-609).  torchvision roi_align semantics

@@ -117,6 +117,9 @@ _SIGS = {
     "inr_nerf_forward_lattice": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_float, P, POINTER(GridDesc), P, P, c_int32,
                                            c_float, P, P]),
     "inr_instance_forward": (c_int32, [P, c_int64, P, c_float, P, POINTER(GridDesc), P, c_int32, P, P]),
+    "inr_instance_lattice": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_float, P, POINTER(GridDesc), P, c_float,
+                                       c_float, P, POINTER(GridDesc), P, c_int32, P, P, P, P]),
+    "inr_instance_volume_stats": (c_int32, [P, P, c_int32, c_int32, c_int32, c_int32, P, c_int64, P, P, P, P]),
     "inr_roi_align_3d_set_mode": (c_int32, [c_int32]),
     "inr_roi_align_3d_forward": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32,
                                            c_int32, c_int32, c_float, P, P]),
@@ -141,7 +144,8 @@ _SIGS = {
 }
 EXPORTS = tuple(_SIGS)
 
-ABI_VERSION = 9          # include/inr.h INR_ABI_VERSION this binding was written against
+ABI_VERSION = 10         # include/inr.h INR_ABI_VERSION this binding was written against
+INSTANCE_STATS_WORKSPACE_BYTES = 512 * 64 * 8 * 4      # include/inr.h INR_INSTANCE_STATS_WORKSPACE_BYTES
 _lib = None
 
 
@@ -155,13 +159,18 @@ def load():
             f"{LIB_PATH} is missing: build it with `python -m instance_nerf_amd.build` "
             "(or __graft_entry__.build()).  There is no CPU fallback.")
     lib = ctypes.CDLL(LIB_PATH)
+    # the version first: a stale library lacks the newer symbols, and binding them would fail with a bare AttributeError
+    version = getattr(lib, "inr_abi_version", None)
+    if version is not None:
+        version.restype, version.argtypes = c_int32, []
+    found = version() if version is not None else None
+    if found != ABI_VERSION:
+        raise RuntimeError(f"{LIB_PATH} ABI version {found} != {ABI_VERSION} (include/inr.h "
+                           "INR_ABI_VERSION): rebuild with `python -m instance_nerf_amd.build --force`")
     for name, (res, args) in _SIGS.items():
         fn = getattr(lib, name)         # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
-    if lib.inr_abi_version() != ABI_VERSION:
-        raise RuntimeError(f"libinr_hip.so ABI version {lib.inr_abi_version()} != {ABI_VERSION} (include/inr.h "
-                           "INR_ABI_VERSION): rebuild with `python -m instance_nerf_amd.build --force`")
     _lib = lib
     return lib
 

@@ -1199,6 +1199,274 @@ __global__ void __launch_bounds__(kFieldThreads, kFieldMinWaves) k_instance_fwd(
   }
 }
 
+// ---- instance-mask lattice extraction (3-D instance segmentation of a trained scene) -------------------------------
+// One launch over the [W, L, H] lattice, walked like k_nerf_fwd_dirs<true> (runs of 16 along W, coordinates clamped to
+// [-bound, bound]): NeRF gather + the two sigma-net layers -> sigma = exp(logit) * density_scale, the sigma the renderer
+// composites; a voxel is occupied when sigma >= sigma_thresh.  A tile none of whose 16 voxels is occupied (wave-uniform
+// ballot) skips the instance gather and MLP - most of a room is empty space, and this skip is where the launch saves its
+// bytes.  Every other tile runs k_instance_fwd's math and reduces the logits IN REGISTERS: arg-max over the K real
+// channels (the zero-padded MFMA channels K..K_pad-1 are excluded - exact zeros would beat all-negative real logits),
+// lowest channel on ties (torch.argmax), max-softmax confidence.  A voxel's channels 16mt + 4q + r are spread over its
+// four q lanes, so both reductions run across lanes j, j+16, j+32, j+48.  No logits go to memory: per voxel 1 label
+// byte, 4 confidence bytes (and the 4-byte density logit when asked for).
+constexpr uint8_t kLabelEmpty = 255;
+constexpr int kNoChannel = 0x7fffffff;
+template <int K_MT>
+__global__ void __launch_bounds__(kFieldThreads, kFieldMinWaves) k_instance_lattice(
+    LatticeDesc lat, float bound, const float2* __restrict__ emb_n, uint32_t emb_n_bytes, GridDesc Gn,
+    const float4* __restrict__ packed_n, float density_scale, float sigma_thresh, const float2* __restrict__ emb_i,
+    uint32_t emb_i_bytes, GridDesc Gi, const float4* __restrict__ packed_i, int K, uint8_t* __restrict__ labels,
+    float* __restrict__ confidence, float* __restrict__ logit_out) {
+  extern __shared__ __attribute__((aligned(16))) float4 wl[];
+  constexpr int kStageN = kCol0 / 4;                         // the sigma net only: no colour net here
+  constexpr int kStageI = (kIns2 + K_MT * 16 * 64) / 4;
+  const float4* wn = wl;
+  const float4* wi = wl + kStageN;
+  for (int i = threadIdx.x; i < kStageN; i += kFieldThreads) wl[i] = packed_n[i];
+  for (int i = threadIdx.x; i < kStageI; i += kFieldThreads) wl[kStageN + i] = packed_i[i];
+  LevelRec* recs_n = reinterpret_cast<LevelRec*>(wl + kStageN + kStageI);
+  LevelRec* recs_i = recs_n + 16;
+  stage_level_recs(Gn, recs_n);
+  stage_level_recs(Gi, recs_i);
+  __syncthreads();
+
+  constexpr int kWaves = kFieldThreads / 64;
+  const int lane = threadIdx.x & 63, q = lane >> 4, j = lane & 15;
+  const int64_t n_tiles = ((int64_t)lat.Wp * lat.L * lat.H) >> 4;
+  const float rb = 2.0f * bound;
+  const TileSched sched = make_sched(n_tiles, kWaves);
+  const bool hashed_n[4] = {slot_all_hashed(Gn, 0), slot_all_hashed(Gn, 1), slot_all_hashed(Gn, 2), slot_all_hashed(Gn, 3)};
+  const bool hashed_i[4] = {slot_all_hashed(Gi, 0), slot_all_hashed(Gi, 1), slot_all_hashed(Gi, 2), slot_all_hashed(Gi, 3)};
+  const __amdgpu_buffer_rsrc_t rsrc_n = __builtin_amdgcn_make_buffer_rsrc((void*)emb_n, 0, (int)emb_n_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsrc_i = __builtin_amdgcn_make_buffer_rsrc((void*)emb_i, 0, (int)emb_i_bytes, 0x00020000);
+  for (int64_t it = 0, tile = sched.tile(0); tile < sched.hi; tile = sched.tile(++it)) {
+    const int64_t m = tile * 16 + j;
+    const int64_t row = m / lat.Wp;
+    const int iw = (int)(m - row * lat.Wp);
+    const int il = (int)(row / lat.H), ih = (int)(row - (int64_t)il * lat.H);
+    const bool valid = iw < lat.W;
+    const int cw = min(iw, lat.W - 1);
+    TileIn me;
+    me.x0 = to_x01(fminf(fmaxf(lat.ax_w[cw], -bound), bound), bound, rb, 0.0f);
+    me.x1 = to_x01(fminf(fmaxf(lat.ax_l[il], -bound), bound), bound, rb, 0.0f);
+    me.x2 = to_x01(fminf(fmaxf(lat.ax_h[ih], -bound), bound), bound, rb, 0.0f);
+    me.oob = oob01(me.x0, me.x1, me.x2);
+    if (me.oob) me.x0 = me.x1 = me.x2 = 0.0f;
+    const int64_t o = ((int64_t)cw * lat.L + il) * lat.H + ih;      // where the voxel lives in [W, L, H]
+    const uint32_t rec_off0 = (uint32_t)q * 4u * (uint32_t)sizeof(LevelRec);
+
+    float logit;
+    {
+      f32x4 enc[2];
+      {
+        Gathered g;
+        uint32_t rec_off = rec_off0;
+        asm volatile("" : "+v"(rec_off));
+        issue_gathers(reinterpret_cast<const LevelRec*>(reinterpret_cast<const char*>(recs_n) + rec_off), hashed_n, rsrc_n,
+                      me.x0, me.x1, me.x2, g);
+        __builtin_amdgcn_sched_barrier(0);
+        blend(g, enc[0], enc[1]);
+      }
+      if (me.oob) enc[0] = enc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+      f32x4 h1[4], h2[1];
+      mlp_layer<4, 2>(wn + kSig0 / 4, lane, enc, h1);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) h1[t] = relu4(h1[t]);
+      mlp_layer<1, 4>(wn + kSig1 / 4, lane, h1, h2);
+      logit = __shfl(h2[0][0], j);                  // row 0 of sample j lives in lane (q = 0, j)
+    }
+    const bool occ = valid && __expf(logit) * density_scale >= sigma_thresh;     // k_nerf_fwd's sigma, times the scale
+    if (logit_out && valid && q == 0) logit_out[o] = logit;
+    if (__ballot(occ) == 0) {                       // wave-uniform: no occupied voxel in this run of 16
+      if (valid && q == 0) {
+        labels[o] = kLabelEmpty;
+        confidence[o] = 0.0f;
+      }
+      continue;
+    }
+
+    f32x4 out[K_MT];
+    {
+      f32x4 enc[2];
+      {
+        Gathered g;
+        uint32_t rec_off = rec_off0;
+        asm volatile("" : "+v"(rec_off));
+        issue_gathers(reinterpret_cast<const LevelRec*>(reinterpret_cast<const char*>(recs_i) + rec_off), hashed_i, rsrc_i,
+                      me.x0, me.x1, me.x2, g);
+        __builtin_amdgcn_sched_barrier(0);
+        blend(g, enc[0], enc[1]);
+      }
+      if (me.oob) enc[0] = enc[1] = f32x4{0.f, 0.f, 0.f, 0.f};
+      f32x4 h1[4], h2[4];
+      mlp_layer<4, 2>(wi + kIns0 / 4, lane, enc, h1);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) h1[t] = relu4(h1[t]);
+      mlp_layer<4, 4>(wi + kIns1 / 4, lane, h1, h2);
+#pragma unroll
+      for (int t = 0; t < 4; ++t) h2[t] = relu4(h2[t]);
+      mlp_layer<K_MT, 4>(wi + kIns2 / 4, lane, h2, out);
+    }
+    // arg-max: this lane's channels in ascending order (strict > keeps the lowest on ties), then across the q lanes
+    float best = 0.0f;
+    int bi = kNoChannel;
+#pragma unroll
+    for (int mt = 0; mt < K_MT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int c = 16 * mt + 4 * q + r;
+        if (c < K && (bi == kNoChannel || out[mt][r] > best)) {
+          best = out[mt][r];
+          bi = c;
+        }
+      }
+#pragma unroll
+    for (int off = 16; off <= 32; off <<= 1) {
+      const float ob = __shfl_xor(best, off);
+      const int oi = __shfl_xor(bi, off);
+      if (oi != kNoChannel && (bi == kNoChannel || ob > best || (ob == best && oi < bi))) {
+        best = ob;
+        bi = oi;
+      }
+    }
+    // max-softmax = 1 / sum_c exp(l_c - max); the butterfly gives every q lane the same sum (a + b == b + a)
+    float s = 0.0f;
+#pragma unroll
+    for (int mt = 0; mt < K_MT; ++mt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (16 * mt + 4 * q + r < K) s += __expf(out[mt][r] - best);
+    s += __shfl_xor(s, 16);
+    s += __shfl_xor(s, 32);
+    if (valid && q == 0) {
+      labels[o] = occ ? (uint8_t)bi : kLabelEmpty;
+      confidence[o] = occ ? 1.0f / s : 0.0f;
+    }
+  }
+}
+
+// Per-channel statistics of a label volume (labels 0..K-1, kLabelEmpty elsewhere): voxel count, inclusive index AABB
+// and the sum of the confidences - bit-reproducible without float atomics.  Pass 1: workgroup b owns a contiguous range
+// of voxels; each wave walks its 64-voxel chunks in order and, for every label present in a chunk, reduces the chunk's
+// confidences of that label with a fixed butterfly and adds the result to its OWN per-wave LDS slot (one writer, program
+// order).  Counts and bounds go through LDS integer atomics (order-independent).  The workgroup then writes, per
+// channel, (count, min iw, il, ih, max iw, il, ih, sum over its waves in wave order) to its fixed slot of the workspace.
+// Pass 2 (k_instance_stats_final) adds the workgroups' slots in a fixed order.
+constexpr int kStatsThreads = 256;
+constexpr int kStatsWaves = kStatsThreads / 64;
+constexpr int kStatsMaxBlocks = 512;
+constexpr int kStatsSlot = 8;                        // int32 words per (workgroup, channel)
+constexpr int64_t kStatsWorkspaceBytes = (int64_t)kStatsMaxBlocks * 64 * kStatsSlot * 4;
+static_assert(kStatsWorkspaceBytes == INR_INSTANCE_STATS_WORKSPACE_BYTES, "include/inr.h");
+
+__device__ __forceinline__ int wave_min(int v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = min(v, __shfl_xor(v, off));
+  return v;
+}
+__device__ __forceinline__ int wave_max(int v) {
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) v = max(v, __shfl_xor(v, off));
+  return v;
+}
+
+__global__ void __launch_bounds__(kStatsThreads) k_instance_stats_partial(const uint8_t* __restrict__ labels,
+                                                                          const float* __restrict__ confidence,
+                                                                          uint32_t N, uint32_t L, uint32_t H, int K,
+                                                                          uint32_t per_block, int* __restrict__ part) {
+  __shared__ int s_cnt[64], s_lo[3][64], s_hi[3][64];
+  __shared__ float s_sum[kStatsWaves][64];
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  if (t < 64) {
+    s_cnt[t] = 0;
+    for (int a = 0; a < 3; ++a) { s_lo[a][t] = 0x7fffffff; s_hi[a][t] = -1; }
+  }
+  s_sum[w][lane] = 0.0f;
+  __syncthreads();
+  const uint32_t lo = blockIdx.x * per_block;
+  const uint32_t hi = min(N, lo + per_block);
+  const uint32_t LH = L * H;
+  for (uint32_t base = lo + (uint32_t)w * 64u; base < hi; base += kStatsThreads) {
+    const uint32_t v = base + (uint32_t)lane;
+    const bool in = v < hi;
+    const int lab = in ? (int)labels[v] : (int)kLabelEmpty;
+    const float cf = in ? confidence[v] : 0.0f;
+    const bool live = lab < K;
+    const uint32_t iw = v / LH, rem = v - iw * LH, il = rem / H, ih = rem - il * H;
+    unsigned long long pending = __ballot(live);
+    while (pending) {
+      const int c = __builtin_amdgcn_readfirstlane(__shfl(lab, (int)__builtin_ctzll(pending)));
+      const bool mine = live && lab == c;
+      const unsigned long long mask = __ballot(mine);
+      pending &= ~mask;
+      float x = mine ? cf : 0.0f;
+#pragma unroll
+      for (int off = 32; off >= 1; off >>= 1) x += __shfl_xor(x, off);
+      const int bw0 = wave_min(mine ? (int)iw : 0x7fffffff), bl0 = wave_min(mine ? (int)il : 0x7fffffff);
+      const int bh0 = wave_min(mine ? (int)ih : 0x7fffffff);
+      const int bw1 = wave_max(mine ? (int)iw : -1), bl1 = wave_max(mine ? (int)il : -1), bh1 = wave_max(mine ? (int)ih : -1);
+      if (lane == 0) {
+        s_sum[w][c] += x;
+        atomicAdd(&s_cnt[c], (int)__popcll(mask));
+        atomicMin(&s_lo[0][c], bw0); atomicMin(&s_lo[1][c], bl0); atomicMin(&s_lo[2][c], bh0);
+        atomicMax(&s_hi[0][c], bw1); atomicMax(&s_hi[1][c], bl1); atomicMax(&s_hi[2][c], bh1);
+      }
+    }
+  }
+  __syncthreads();
+  if (t < K) {
+    float sum = 0.0f;
+    for (int ww = 0; ww < kStatsWaves; ++ww) sum += s_sum[ww][t];
+    int* slot = part + ((int64_t)blockIdx.x * 64 + t) * kStatsSlot;
+    slot[0] = s_cnt[t];
+    slot[1] = s_lo[0][t]; slot[2] = s_lo[1][t]; slot[3] = s_lo[2][t];
+    slot[4] = s_hi[0][t]; slot[5] = s_hi[1][t]; slot[6] = s_hi[2][t];
+    slot[7] = __float_as_int(sum);
+  }
+}
+
+// 8 groups of 64 threads: thread (g, c) folds workgroups g, g + 8, g + 16, ... of channel c in that order, then thread
+// (0, c) folds the eight groups in group order - a fixed order (bit-reproducible) with 1/8 of the serial chain of one
+// thread per channel (0.13 ms at 512 workgroups)
+constexpr int kStatsFinalGroups = 8;
+__global__ void __launch_bounds__(64 * kStatsFinalGroups) k_instance_stats_final(const int* __restrict__ part, int n_blocks,
+                                                                                 int K, int32_t* __restrict__ counts,
+                                                                                 int32_t* __restrict__ boxes,
+                                                                                 float* __restrict__ conf_sum) {
+  __shared__ int s_b[kStatsFinalGroups][7][64];
+  __shared__ float s_s[kStatsFinalGroups][64];
+  const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
+  int cnt = 0, b[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, -1, -1, -1};
+  float sum = 0.0f;
+  if (c < K) {
+    for (int blk = g; blk < n_blocks; blk += kStatsFinalGroups) {
+      const int* slot = part + ((int64_t)blk * 64 + c) * kStatsSlot;
+      cnt += slot[0];
+      for (int a = 0; a < 3; ++a) {
+        b[a] = min(b[a], slot[1 + a]);
+        b[3 + a] = max(b[3 + a], slot[4 + a]);
+      }
+      sum += __int_as_float(slot[7]);
+    }
+  }
+  s_b[g][0][c] = cnt;
+  for (int a = 0; a < 6; ++a) s_b[g][1 + a][c] = b[a];
+  s_s[g][c] = sum;
+  __syncthreads();
+  if (g != 0 || c >= K) return;
+  for (int gg = 1; gg < kStatsFinalGroups; ++gg) {
+    cnt += s_b[gg][0][c];
+    for (int a = 0; a < 3; ++a) {
+      b[a] = min(b[a], s_b[gg][1 + a][c]);
+      b[3 + a] = max(b[3 + a], s_b[gg][4 + a][c]);
+    }
+    sum += s_s[gg][c];
+  }
+  counts[c] = cnt;
+  for (int a = 0; a < 6; ++a) boxes[c * 6 + a] = cnt ? b[a] : -1;
+  conf_sum[c] = sum;
+}
+
 // ---- instance MLP input gradients (training) ----------------------------------------------------------------
 // The chain dL/dlogits -> dL/dz2 -> dL/dz1 -> dL/denc is the same transposed formulation with W^T as the A
 // operand: G^T = W^T . dY^T, so every layer's D registers are again the next layer's B operand.  Sections of
@@ -2756,6 +3024,78 @@ int inr_instance_forward_enc(const float* x, int64_t M, const int32_t* n_samples
     default: k_instance_fwd<4, 2><<<grid_for(k_instance_fwd<4, 2>, lds, n_tiles), kFieldThreads, lds, st>>>(x, M, n_samples_dev, bound, e, eb, G, p, logits, enc, nullptr, nullptr); break;
   }
   return check_launch("instance_forward_enc");
+}
+
+int inr_instance_lattice(const float* ax_w, const float* ax_l, const float* ax_h, int32_t W, int32_t L, int32_t H,
+                         float bound, const float* nerf_embeddings, const inr_grid_desc* nerf_desc, const float* nerf_packed,
+                         float density_scale, float sigma_thresh, const float* inst_embeddings,
+                         const inr_grid_desc* inst_desc, const float* inst_packed, int32_t K, uint8_t* labels,
+                         float* confidence, float* density_logit, inr_stream_t s) {
+  INR_REQUIRE(W >= 0 && L >= 0 && H >= 0, "W, L, H must be >= 0");
+  INR_REQUIRE(K >= 1 && K <= 64, "K must be 1..64 (packed with K_pad = 16 * ceil(K / 16) output rows)");
+  INR_REQUIRE(nerf_desc && inst_desc, "null grid descriptor");
+  INR_REQUIRE(ax_w && ax_l && ax_h && nerf_embeddings && nerf_packed && inst_embeddings && inst_packed && labels &&
+                  confidence, "null pointer");
+  INR_REQUIRE(!std::isnan(bound) && bound > 0.0f, "bound must be > 0");
+  INR_REQUIRE(!std::isnan(sigma_thresh) && !std::isnan(density_scale), "sigma_thresh / density_scale must not be NaN");
+  INR_REQUIRE((((uintptr_t)nerf_embeddings | (uintptr_t)inst_embeddings) & 7) == 0 &&
+                  (((uintptr_t)nerf_packed | (uintptr_t)inst_packed) & 15) == 0 &&
+                  (((uintptr_t)confidence | (uintptr_t)density_logit) & 3) == 0,
+              "embeddings/packed/confidence/density_logit misaligned");
+  INR_REQUIRE((int64_t)W * L * H < (1ll << 31), "lattice of 2^31 voxels or more");
+  GridDesc Gn, Gi;
+  int rc = make_grid_desc(nerf_desc, Gn);
+  if (rc) return rc;
+  rc = make_grid_desc(inst_desc, Gi);
+  if (rc) return rc;
+  const uint64_t bn = (uint64_t)nerf_desc->offsets[nerf_desc->num_levels] * 8ull;
+  const uint64_t bi = (uint64_t)inst_desc->offsets[inst_desc->num_levels] * 8ull;
+  INR_REQUIRE(bn < (1ull << 31) && bi < (1ull << 31), "table larger than 2 GiB is not addressable by the 32-bit gather offsets");
+  if ((int64_t)W * L * H == 0) return INR_OK;
+  LatticeDesc lat{ax_w, ax_l, ax_h, W, L, H, (W + 15) / 16 * 16};
+  const int K_MT = (K + 15) / 16;
+  const size_t lds = (size_t)(kCol0 + kIns2 + K_MT * 16 * 64) * sizeof(float) + 2 * kLevelRecBytes;
+  const int64_t n_tiles = (int64_t)lat.Wp * L * H / 16;
+  const float2* en = reinterpret_cast<const float2*>(nerf_embeddings);
+  const float2* ei = reinterpret_cast<const float2*>(inst_embeddings);
+  const float4* pn = reinterpret_cast<const float4*>(nerf_packed);
+  const float4* pk = reinterpret_cast<const float4*>(inst_packed);
+  hipStream_t st = as_stream(s);
+#define INR_IL_LAUNCH(KMT)                                                                                              \
+  k_instance_lattice<KMT><<<grid_for(k_instance_lattice<KMT>, lds, n_tiles), kFieldThreads, lds, st>>>(                 \
+      lat, bound, en, (uint32_t)bn, Gn, pn, density_scale, sigma_thresh, ei, (uint32_t)bi, Gi, pk, K, labels, confidence, \
+      density_logit)
+  switch (K_MT) {
+    case 1: INR_IL_LAUNCH(1); break;
+    case 2: INR_IL_LAUNCH(2); break;
+    case 3: INR_IL_LAUNCH(3); break;
+    default: INR_IL_LAUNCH(4); break;
+  }
+#undef INR_IL_LAUNCH
+  return check_launch("instance_lattice");
+}
+
+int inr_instance_volume_stats(const uint8_t* labels, const float* confidence, int32_t W, int32_t L, int32_t H, int32_t K,
+                              void* workspace, int64_t workspace_bytes, int32_t* counts, int32_t* boxes, float* conf_sum,
+                              inr_stream_t s) {
+  INR_REQUIRE(W >= 0 && L >= 0 && H >= 0, "W, L, H must be >= 0");
+  INR_REQUIRE(K >= 1 && K <= 64, "K must be 1..64");
+  INR_REQUIRE(workspace_bytes >= kStatsWorkspaceBytes, "workspace smaller than INR_INSTANCE_STATS_WORKSPACE_BYTES");
+  INR_REQUIRE(labels && confidence && workspace && counts && boxes && conf_sum, "null pointer");
+  INR_REQUIRE((((uintptr_t)confidence | (uintptr_t)workspace | (uintptr_t)counts | (uintptr_t)boxes | (uintptr_t)conf_sum) & 3) == 0,
+              "confidence/workspace/outputs misaligned");
+  const int64_t N = (int64_t)W * L * H;
+  INR_REQUIRE(N < (1ll << 31), "volume of 2^31 voxels or more");
+  // at least 16 chunks of 64 voxels per workgroup, at most kStatsMaxBlocks workgroups
+  const int64_t per_min = 16 * 64;
+  const int n_blocks = (int)std::max<int64_t>(1, std::min<int64_t>(kStatsMaxBlocks, (N + per_min - 1) / per_min));
+  const int64_t per_block = (N + n_blocks - 1) / n_blocks;
+  hipStream_t st = as_stream(s);
+  int* part = reinterpret_cast<int*>(workspace);
+  k_instance_stats_partial<<<n_blocks, kStatsThreads, 0, st>>>(labels, confidence, (uint32_t)N, (uint32_t)L, (uint32_t)H, K,
+                                                               (uint32_t)per_block, part);
+  k_instance_stats_final<<<1, 64 * kStatsFinalGroups, 0, st>>>(part, n_blocks, K, counts, boxes, conf_sum);
+  return check_launch("instance_volume_stats");
 }
 
 static size_t head_bwd_lds() { return (size_t)(kHbFwdFloats + kBwdFloats + kHbStageFloats) * sizeof(float); }

@@ -137,3 +137,115 @@ def write_features_npz(path, rgbsigma, bbox_min, bbox_max, scale=1.0, offset=(0.
                         scale=np.float32(scale), offset=np.asarray(offset, dtype=np.float32),
                         from_mitsuba=np.bool_(from_mitsuba))
     return path
+
+
+# ---- 3-D instance masks of a trained instance field ---------------------------------------------------------------
+LABEL_EMPTY = 255        # label of an unoccupied voxel
+
+
+def volume_stats(labels, confidence, K):
+    """Per-channel statistics of a label volume (uint8 [W, L, H], ``LABEL_EMPTY`` = unoccupied): -> (counts int64 [K],
+    boxes int64 [K, 6] = inclusive voxel-index bounds (min iw, il, ih, max iw, il, ih; -1 for an empty channel),
+    conf_sum float32 [K]), on the volume's device.  On the GPU (K <= 64) one bit-reproducible HIP call
+    (``inr_instance_volume_stats``: fixed per-workgroup slots, fixed-order final pass); otherwise numpy on the host
+    (float64 sums)."""
+    W, L, H = (int(v) for v in labels.shape)
+    if labels.is_cuda and 1 <= K <= 64:
+        from . import _lib
+        lib = _lib.load()
+        dev = labels.device
+        ws = torch.empty(_lib.INSTANCE_STATS_WORKSPACE_BYTES // 4, dtype=torch.int32, device=dev)
+        counts = torch.empty(K, dtype=torch.int32, device=dev)
+        boxes = torch.empty(K, 6, dtype=torch.int32, device=dev)
+        csum = torch.empty(K, dtype=torch.float32, device=dev)
+        _lib.check(lib.inr_instance_volume_stats(_lib.ptr(labels.contiguous(), torch.uint8, "labels"),
+                                                 _lib.ptr(confidence.contiguous(), torch.float32, "confidence"), W, L, H, K,
+                                                 _lib.ptr(ws), _lib.INSTANCE_STATS_WORKSPACE_BYTES, _lib.ptr(counts),
+                                                 _lib.ptr(boxes), _lib.ptr(csum), _lib.stream_ptr()), "instance_volume_stats")
+        return counts.long(), boxes.long(), csum
+    lab = labels.detach().cpu().numpy().reshape(-1).astype(np.int64)
+    cf = confidence.detach().cpu().numpy().reshape(-1).astype(np.float64)
+    live = lab < K
+    idx = np.nonzero(live)[0]
+    ch = lab[idx]
+    counts = np.bincount(ch, minlength=K)[:K]
+    csum = np.bincount(ch, weights=cf[idx], minlength=K)[:K].astype(np.float32)
+    coords = np.stack(np.unravel_index(idx, (W, L, H)), 1)
+    boxes = np.full((K, 6), -1, dtype=np.int64)
+    big = np.iinfo(np.int64).max
+    lo = np.full((K, 3), big, dtype=np.int64)
+    hi = np.full((K, 3), -1, dtype=np.int64)
+    np.minimum.at(lo, ch, coords)
+    np.maximum.at(hi, ch, coords)
+    has = counts > 0
+    boxes[has, :3], boxes[has, 3:] = lo[has], hi[has]
+    dev = labels.device
+    return (torch.from_numpy(counts.astype(np.int64)).to(dev), torch.from_numpy(boxes).to(dev),
+            torch.from_numpy(csum).to(dev))
+
+
+def _instances_composable(model, bbox_min, bbox_max, res, sigma_thresh, chunk):
+    """The composable form of the fused launch, with its semantics: voxel centres clamped to [-bound, bound], occupied
+    when density_scale * sigma >= sigma_thresh, arg-max over the K real channels (torch.argmax: lowest on ties), max-softmax
+    confidence, ``LABEL_EMPTY`` / 0 elsewhere.  ``density()`` and ``instance()`` per chunk of points."""
+    dev = next(model.parameters()).device
+    b = float(model.bound)
+    pts = lattice(bbox_min, bbox_max, res, dev)
+    labels = torch.full((pts.shape[0],), LABEL_EMPTY, dtype=torch.uint8, device=dev)
+    conf = torch.zeros(pts.shape[0], dtype=torch.float32, device=dev)
+    for s in range(0, pts.shape[0], chunk):
+        x = pts[s:s + chunk].clamp(-b, b).contiguous()
+        occ = model.density(x)["sigma"] * model.density_scale >= sigma_thresh
+        if not bool(occ.any()):
+            continue
+        logits = model.instance(x)[:, :model.num_instances].float()       # the K real channels only
+        mx, arg = logits.amax(1), torch.argmax(logits, 1)
+        c = 1.0 / torch.exp(logits - mx[:, None]).sum(1)
+        labels[s:s + chunk] = torch.where(occ, arg.to(torch.uint8), torch.full_like(labels[s:s + chunk], LABEL_EMPTY))
+        conf[s:s + chunk] = torch.where(occ, c, torch.zeros_like(c))
+    W, L, H = (int(v) for v in res)
+    return labels.view(W, L, H), conf.view(W, L, H)
+
+
+@torch.no_grad()
+def extract_instances(model, bbox_min=None, bbox_max=None, max_side=160, res=None, sigma_thresh=None, fused=True,
+                      chunk=1 << 20):
+    """The trained instance field as a 3-D segmentation on the lattice of ``extract_rgbsigma`` (voxel centres, longest
+    side ``max_side``, default box [-bound, bound]^3).  A voxel is occupied when ``density_scale * sigma`` (the sigma the
+    renderer composites) is >= ``sigma_thresh`` (default ``model.density_thresh``).  -> dict:
+
+    * ``labels`` uint8 [W, L, H]: the arg-max instance channel 0..K-1 of an occupied voxel (channel 0 = background /
+      walls, lowest channel on ties as ``torch.argmax``), ``LABEL_EMPTY`` (255) elsewhere;
+    * ``confidence`` float32 [W, L, H]: its softmax probability, 0 where unoccupied;
+    * ``res`` int64 [3]; ``counts`` int64 [K] voxels per channel; ``boxes`` int64 [K, 6] inclusive voxel-index bounds
+      (min iw, il, ih, max iw, il, ih; -1 for an empty channel); ``scores`` float32 [K] mean confidence of the channel's
+      voxels (0 when empty).
+
+    Tensors stay on the model's device.  The fused path is one HIP launch for the labels (``NeRFNetwork.instance_lattice``)
+    and one for the statistics; two calls give identical bits.  ``fused=False`` (and shapes the fused kernels do not
+    cover) runs the composable path - ``density()`` + ``instance()`` over chunks of points - with the same semantics."""
+    if not getattr(model, "num_instances", 0):
+        raise ValueError("extract_instances: the model has no instance head (num_instances = 0)")
+    dev = next(model.parameters()).device
+    b = float(model.bound)
+    bbox_min = np.asarray([-b, -b, -b] if bbox_min is None else bbox_min, dtype=np.float32)
+    bbox_max = np.asarray([b, b, b] if bbox_max is None else bbox_max, dtype=np.float32)
+    res = grid_resolution(bbox_min, bbox_max, max_side) if res is None else np.asarray(res, dtype=np.int64)
+    thresh = float(model.density_thresh if sigma_thresh is None else sigma_thresh)
+    K = int(model.num_instances)
+    if K >= LABEL_EMPTY:
+        raise ValueError(f"extract_instances: {K} instance channels do not fit the uint8 labels (at most {LABEL_EMPTY - 1})")
+    was_training = model.training
+    model.eval()
+    try:
+        out = None
+        if fused and hasattr(model, "instance_lattice"):
+            out = model.instance_lattice(_cached_axes(bbox_min, bbox_max, res, dev), thresh)
+        if out is None:
+            out = _instances_composable(model, bbox_min, bbox_max, res, thresh, chunk)
+    finally:
+        model.train(was_training)
+    labels, conf = out
+    counts, boxes, csum = volume_stats(labels, conf, K)
+    scores = torch.where(counts > 0, csum / counts.clamp_min(1).float(), torch.zeros_like(csum))
+    return {"labels": labels, "confidence": conf, "res": res, "counts": counts, "boxes": boxes, "scores": scores}

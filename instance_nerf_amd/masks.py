@@ -193,3 +193,39 @@ def project_3d_masks(model, masks, bbox_min, bbox_max, poses, intrinsics, H, W, 
                     save_png_gray(os.path.join(proj_dir, f"{name}_{i + 1}.png"), out[v, i].astype(np.uint8) * 255)
     model.train(was_training)
     return out
+
+
+def write_instance_masks_npz(path, result, labels=None, min_voxels=1):
+    """Writes the 3-D segmentation of ``extract.extract_instances`` as ``masks/<scene>.npz`` in the layout
+    ``load_3d_masks`` reads (run_rcnn.py:652-666): ``masks`` bool [k, W, L, H], ``scores`` float32 [k], ``labels`` int64
+    [k] (``labels``: the caller's class per instance, default all ones), ``boxes`` float32 [k, 6] in grid units
+    (x1, y1, z1, x2, y2, z2 = min voxel index, max voxel index + 1).
+
+    Mask i is instance id i + 1 - the id rule of ``load_3d_masks`` - so k = K - 1: channel 0 (background / walls) is
+    never a mask.  The masks stay in ID ORDER, not sorted by score as the NeRF-RCNN writer sorts its detections, so that
+    projecting and matching them reproduces the field's own ids.  An instance with fewer than ``min_voxels`` voxels keeps
+    its slot with an empty mask, score 0 and a zero box.  -> path."""
+    def host(v):
+        return v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+    lab = host(result["labels"])
+    if lab.ndim != 3:
+        raise ValueError("result['labels'] must be [W, L, H]")
+    counts, boxes, scores = host(result["counts"]), host(result["boxes"]), host(result["scores"])
+    k = int(counts.shape[0]) - 1
+    if k < 0:
+        raise ValueError("result holds no instance channel")
+    cls = np.ones(k, dtype=np.int64) if labels is None else np.asarray(labels, dtype=np.int64).reshape(-1)
+    if cls.shape != (k,):
+        raise ValueError(f"labels must hold one class per instance id 1..{k}, got shape {cls.shape}")
+    keep = counts[1:] >= max(int(min_voxels), 1)
+    masks = np.zeros((k,) + lab.shape, dtype=bool)
+    for i in np.nonzero(keep)[0]:
+        masks[i] = lab == i + 1
+    out_scores = np.where(keep, scores[1:], 0.0).astype(np.float32)
+    out_boxes = np.zeros((k, 6), dtype=np.float32)
+    b = boxes[1:].astype(np.float32)
+    out_boxes[keep, :3] = b[keep, :3]
+    out_boxes[keep, 3:] = b[keep, 3:] + 1.0
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.savez_compressed(path, masks=masks, scores=out_scores, labels=cls, boxes=out_boxes)
+    return path

@@ -853,6 +853,34 @@ class NeRFNetwork(NeRFRenderer):
                                                float(logit_min), ptr(out), stream_ptr()), "nerf_forward_lattice")
         return out
 
+    @torch.no_grad()
+    def instance_lattice(self, axes, sigma_thresh, want_logit=False):
+        """3-D instance labels of the lattice ``axes = (ax_w [W], ax_l [L], ax_h [H])`` (float32, on the device) in one
+        launch (``inr_instance_lattice``): -> (labels uint8 [W, L, H], confidence float [W, L, H]) and, with
+        ``want_logit``, the density logit float [W, L, H] as a third element.  A voxel is occupied when
+        ``density_scale * sigma >= sigma_thresh``; occupied voxels carry the arg-max over the K instance channels
+        (lowest on ties) and its softmax probability, the others 255 and 0.  Coordinates are clamped to
+        [-bound, bound].  None when the fused kernels do not apply."""
+        if not (self._fusable and self.num_instances and self._fusable_inst):
+            return None
+        lib = _lib.load()
+        ax = [a.contiguous().float() for a in axes]
+        W, L, H = (int(a.shape[0]) for a in ax)
+        dev = ax[0].device
+        labels = torch.empty(W, L, H, dtype=torch.uint8, device=dev)
+        conf = torch.empty(W, L, H, dtype=torch.float32, device=dev)
+        logit = torch.empty(W, L, H, dtype=torch.float32, device=dev) if want_logit else None
+        if W * L * H:
+            check(lib.inr_instance_lattice(ptr(ax[0], torch.float32, "ax_w"), ptr(ax[1], torch.float32, "ax_l"),
+                                           ptr(ax[2], torch.float32, "ax_h"), W, L, H, float(self.bound),
+                                           ptr(self.encoder.embeddings.data, torch.float32), self.encoder.desc,
+                                           ptr(self._packed_weights("nerf")), float(self.density_scale),
+                                           float(sigma_thresh), ptr(self.instance_encoder.embeddings.data, torch.float32),
+                                           self.instance_encoder.desc, ptr(self._packed_weights("instance")),
+                                           self.num_instances, ptr(labels, torch.uint8), ptr(conf),
+                                           ptr(logit, allow_none=True), stream_ptr()), "instance_lattice")
+        return (labels, conf, logit) if want_logit else (labels, conf)
+
     # ---- upstream API -----------------------------------------------------------------------------
     def forward(self, x, d):
         """x [M,3] in [-bound,bound], d [M,3] unit -> sigma [M], color [M,3]."""

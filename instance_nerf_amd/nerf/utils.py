@@ -1525,6 +1525,24 @@ class Trainer:
         self.model.train()
         return written
 
+    def save_instance_masks(self, save_path=None, name=None, **extract_kwargs):
+        """Writes the trained instance field's 3-D segmentation (``extract.extract_instances`` with ``extract_kwargs``)
+        as ``<save_path>/<name>.npz`` (default ``<workspace>/masks/<self.name>.npz``) in the layout
+        ``masks.load_3d_masks`` reads (``masks.write_instance_masks_npz``; ``labels`` / ``min_voxels`` are passed on to
+        it).  Evaluates the parameters ``test`` renders with, in eval mode, and restores the previous mode.  -> path."""
+        from ..extract import extract_instances
+        from ..masks import write_instance_masks_npz
+        write_kw = {k: extract_kwargs.pop(k) for k in ("labels", "min_voxels") if k in extract_kwargs}
+        save_path = save_path or os.path.join(self.workspace or ".", "masks")
+        path = os.path.join(save_path, f"{name or self.name}.npz")
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            result = extract_instances(self.model, **extract_kwargs)
+        finally:
+            self.model.train(was_training)
+        return write_instance_masks_npz(path, result, **write_kw)
+
     # -- checkpoint (upstream keys: epoch, global_step, stats, model, optimizer, lr_scheduler, ema, mean_count, mean_density)
     def save_checkpoint(self, name=None, full=False, best=False, remove_old=True, path=None):
         """``full``: with optimizer / scheduler / EMA state (to resume training); ``best``: written to
