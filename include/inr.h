@@ -37,8 +37,9 @@ extern "C" {
 /* Bumped whenever an existing prototype changes or an entry point is removed (round 2 changed four argument lists
  * without a bump: a stale library or an external caller built against the old header was only rejected by accident).
  * instance_nerf_amd/_lib.py refuses a library whose version differs from the one it was written against.
- * 10: inr_instance_lattice, inr_instance_volume_stats. */
-#define INR_ABI_VERSION 10
+ * 10: inr_instance_lattice, inr_instance_volume_stats.
+ * 11: the fp16 variants folded into their base entry points as a `numerics` argument (INR_NUMERICS_*). */
+#define INR_ABI_VERSION 11
 #define INR_MAX_LEVELS 16
 
 enum {
@@ -49,6 +50,17 @@ enum {
 };
 
 typedef void* inr_stream_t; /* a hipStream_t; NULL = the null stream */
+
+/* `numerics` of the fused field entry points: 0 is the default (fp32 table, MLP GEMMs in the three-pass bf16 split that
+ * keeps results fp32-class); each entry point lists the other values it accepts, anything else is INR_EINVAL.  Both
+ * bits together are upstream's `-O` numerics, opt-in, for fields that are only evaluated (inference; the frozen NeRF of
+ * the instance stage): NeRFNetwork.half_table + mlp_fp16, Trainer(fp16=True).  INR_NUMERICS_MLP_F16 does not exist in
+ * the -DINR_MLP_FP32 build.                                                                                          */
+enum {
+  INR_NUMERICS_TABLE_F16 = 1, /* the table is an fp16 copy (T x 2 binary16): 11 significant bits, outputs ~1e-3 off  */
+  INR_NUMERICS_MLP_F16 = 2    /* ONE fp16 MFMA pass per MLP GEMM (weights and activations rounded to fp16, fp32
+                                 accumulation; 2^-12 relative per operand), weights packed with this same bit          */
+};
 
 /* Host-side description of a multiresolution hash grid.  Filled by
  * the caller (instance_nerf_amd.gridencoder.level_table) so host and device
@@ -367,54 +379,38 @@ int inr_sh_table_q(const float* d /*[N,3]*/, int64_t N, float* out /*[N,16], 16-
  * Weights are nn.Linear [out,in] row-major fp32, no bias:
  *   sigma_w0[64,32] sigma_w1[16,64] color_w0[64,31] color_w1[64,64] color_w2[3,64]
  *   inst_w0[64,32] inst_w1[64,64] inst_w2[K,64] (K <= 64, K % 16 == 0: a caller with another K zero-pads the rows, as NeRFNetwork does)
- * inr_field_pack_* reorder them (on the host) into MFMA fragment order; the
- * packed buffer is then copied to the device by the caller.                              */
+ * inr_*_pack_weights reorder them (on the host) into MFMA fragment order; the packed buffer is then copied to the
+ * device by the caller.  numerics:
+ *   - 0: the weights of the default numerics;
+ *   - INR_NUMERICS_MLP_F16: fp16 values in the head slots of the same size and fragment layout, for the entry points
+ *     called with that bit.                                                                   */
 int64_t inr_nerf_packed_floats(void);
 int inr_nerf_pack_weights(const float* sigma_w0, const float* sigma_w1, const float* color_w0,
-                          const float* color_w1, const float* color_w2, float* packed /*host*/);
+                          const float* color_w1, const float* color_w2, float* packed /*host*/, int32_t numerics);
 int64_t inr_instance_packed_floats(int32_t K);
 int inr_instance_pack_weights(const float* w0, const float* w1, const float* w2, int32_t K,
-                              float* packed /*host*/);
+                              float* packed /*host*/, int32_t numerics);
 /* sigma[M] (= exp(h0) * density_scale), rgb[M,3] (nullable -> density only),
  * geo_feat[M,15] (nullable).  n_samples_dev: optional device int32 holding the
- * live row count (<= M); rows past it are skipped.                                           */
+ * live row count (<= M); rows past it are skipped.  numerics:
+ *   - 0: fp32 table (8-byte aligned);
+ *   - INR_NUMERICS_TABLE_F16 | INR_NUMERICS_MLP_F16 (upstream's `-O`; the FROZEN NeRF of the instance stage): fp16
+ *     table (4-byte aligned), weights packed with INR_NUMERICS_MLP_F16; rgb required, geo_feat must be NULL.        */
 int inr_nerf_forward(const float* x, const float* d, int64_t M, const int32_t* n_samples_dev,
-                     float bound, const float* embeddings, const inr_grid_desc* desc /*host*/,
+                     float bound, const void* embeddings, const inr_grid_desc* desc /*host*/,
                      const float* packed /*device*/, float density_scale, float* sigma, float* rgb,
-                     float* geo_feat, inr_stream_t s);
-/* inr_nerf_forward (sigma + rgb) with upstream's `-O` numerics, opt-in: fp16 copy of the table (T x 2 binary16),
- * weights from inr_nerf_pack_weights_f16, one fp16 MFMA pass per MLP GEMM.  Used for the FROZEN NeRF of the instance
- * stage when Trainer(fp16=True) / NeRFNetwork.half_table + mlp_fp16 are set.  Not in the -DINR_MLP_FP32 build.   */
-int inr_nerf_forward_fast(const float* x, const float* d, int64_t M, const int32_t* n_samples_dev, float bound,
-                          const void* embeddings_half, const inr_grid_desc* desc /*host*/,
-                          const float* packed_f16 /*device*/, float density_scale, float* sigma, float* rgb,
-                          inr_stream_t s);
+                     float* geo_feat, int32_t numerics, inr_stream_t s);
 /* Fused-frame variant of inr_nerf_forward: x01 [M,3] already normalised by inr_march_rays_patch_write
  * (normalise = 1), directions given as a per-sample ray id + the per-ray table of inr_sh_table_q
- * ([N,4,4]: row q holds SH components q, 4+q, 8+q, 12+q).  Same results, ~100 VALU instructions per tile less. */
+ * ([N,4,4]: row q holds SH components q, 4+q, 8+q, 12+q).  Same results, ~100 VALU instructions per tile less.
+ * numerics, any combination of the two bits (opt-in, inference):
+ *   - INR_NUMERICS_TABLE_F16 (NeRFNetwork.half_table): embeddings is the fp16 copy of the table (4 bytes per row: 512
+ *     instead of 1024 algorithmic bytes per sample); index arithmetic and blending are unchanged;
+ *   - INR_NUMERICS_MLP_F16 (NeRFNetwork.mlp_fp16): weights packed with INR_NUMERICS_MLP_F16.                       */
 int inr_nerf_forward_table(const float* x01, const int32_t* ray_ids, const float* sh_table_q, int64_t M,
-                           float bound, const float* embeddings, const inr_grid_desc* desc /*host*/,
+                           float bound, const void* embeddings, const inr_grid_desc* desc /*host*/,
                            const float* packed /*device*/, float density_scale, float* sigma, float* rgb,
-                           inr_stream_t s);
-/* The same launch on a HALF-PRECISION copy of the table (fp16 [T,2], 4 bytes per row; upstream's `-O` / fp16 storage,
- * here an opt-in for inference: NeRFNetwork.half_table).  Index arithmetic, blending and the MLPs are unchanged (fp32);
- * the table VALUES carry 11 significant bits, so outputs differ from the fp32 table's by ~1e-3 relative.  512 instead of
- * 1024 algorithmic bytes per sample.  embeddings_half: device pointer to T x 2 IEEE binary16 values.               */
-int inr_nerf_forward_table_half(const float* x01, const int32_t* ray_ids, const float* sh_table_q, int64_t M,
-                                float bound, const void* embeddings_half, const inr_grid_desc* desc /*host*/,
-                                const float* packed /*device*/, float density_scale, float* sigma, float* rgb,
-                                inr_stream_t s);
-/* The same launch with upstream's `-O` numerics (opt-in, inference: NeRFNetwork.mlp_fp16): the MLP GEMMs take ONE fp16
- * MFMA pass - weights and activations rounded to fp16, fp32 accumulation - instead of the three-pass bf16 split that
- * keeps the default path fp32-class; 2^-12 relative per operand.  `packed` must come from inr_nerf_pack_weights_f16
- * (same size and fragment layout as inr_nerf_pack_weights, fp16 values in the head slots).  embeddings: the fp32
- * table, or the fp16 copy when table_is_half != 0.  Not available in the -DINR_MLP_FP32 build.                     */
-int inr_nerf_pack_weights_f16(const float* sigma_w0, const float* sigma_w1, const float* color_w0,
-                              const float* color_w1, const float* color_w2, float* packed /*host*/);
-int inr_nerf_forward_table_fast(const float* x01, const int32_t* ray_ids, const float* sh_table_q, int64_t M,
-                                float bound, const void* embeddings, int32_t table_is_half,
-                                const inr_grid_desc* desc /*host*/, const float* packed /*device*/,
-                                float density_scale, float* sigma, float* rgb, inr_stream_t s);
+                           int32_t numerics, inr_stream_t s);
 /* Sliced variant of inr_nerf_forward_table (round 5; same results bit for bit; fp32 table, 16 levels, hashed fine
  * levels): the three finest levels (13..15) are evaluated first, one level at a time over all samples - a hashed level
  * is 4 MiB, exactly one XCD's L2, and where those levels are finer than the spacing of a frame's samples nothing but a
@@ -591,39 +587,29 @@ int inr_roi_align_3d_backward_ws(const float* grad_out, const float* rois, const
  * alive-ray loop of NeRFRenderer.run_cuda achieves, a5, without host round trips).  Same results as
  * inr_nerf_forward + inr_composite_rays_patch_forward up to fp32 rounding.  weights [M] nullable (w per sample,
  * 0 when skipped); evaluated: device uint64 [33], ZEROED BY THE CALLER - [0] receives the number of samples evaluated,
- * [1..32] are the cursors of the launch's dynamic group schedule (scratch).                                        */
+ * [1..32] are the cursors of the launch's dynamic group schedule (scratch).  numerics:
+ *   - 0: fp32 table;
+ *   - INR_NUMERICS_TABLE_F16 | INR_NUMERICS_MLP_F16 (upstream's `-O`, NeRFNetwork.half_table + mlp_fp16): fp16
+ *     table, weights packed with INR_NUMERICS_MLP_F16.                                                              */
 int inr_nerf_render(const float* xyzs, const float* deltas, const int32_t* rays, const float* rays_d /*[N,3]*/,
-                    int64_t N, int64_t M, float bound, const float* embeddings, const inr_grid_desc* desc /*host*/,
+                    int64_t N, int64_t M, float bound, const void* embeddings, const inr_grid_desc* desc /*host*/,
                     const float* packed /*device*/, float density_scale, float T_thresh, float* weights_sum,
                     float* depth, float* image, float* weights, uint64_t* evaluated, int32_t x_is_01 /* xyzs are the
-                    normalised coordinates of the patch writer's table feed */, inr_stream_t s);
-/* The same launch with upstream's `-O` numerics (opt-in: NeRFNetwork.half_table + mlp_fp16): fp16 copy of the table,
- * weights from inr_nerf_pack_weights_f16, one fp16 MFMA pass per MLP GEMM.  Not in the -DINR_MLP_FP32 build.      */
-int inr_nerf_render_fast(const float* xyzs, const float* deltas, const int32_t* rays, const float* rays_d, int64_t N,
-                         int64_t M, float bound, const void* embeddings_half, const inr_grid_desc* desc /*host*/,
-                         const float* packed_f16 /*device*/, float density_scale, float T_thresh, float* weights_sum,
-                         float* depth, float* image, float* weights, uint64_t* evaluated, int32_t x_is_01,
-                         inr_stream_t s);
+                    normalised coordinates of the patch writer's table feed */, int32_t numerics, inr_stream_t s);
 
 /* Instance logits rendered in place (inference, patch-interleaved layout): extra_out[ray][ch] =
  * sum_k weights[slot(ray,k)] * logits(xyzs[slot(ray,k)])[ch]; the [M,K] logits never exist in memory.
  * xyzs/weights [M] in the patch-interleaved layout (inr_march_rays_patch_write / the weights output of
  * inr_composite_rays_patch_forward), rays [N,3] from the count pass, extra_out [N,K].  x_is_01 != 0: xyzs holds
- * the normalised coordinates (x + bound) / (2 bound) the patch writer emits with normalise = 1.          */
+ * the normalised coordinates (x + bound) / (2 bound) the patch writer emits with normalise = 1.  numerics:
+ *   - 0: fp32 table;
+ *   - INR_NUMERICS_TABLE_F16 | INR_NUMERICS_MLP_F16 (upstream's `-O`, NeRFNetwork.half_table + mlp_fp16): fp16 copy
+ *     of the instance table, weights packed with INR_NUMERICS_MLP_F16.                                            */
 int inr_instance_render(const float* xyzs, const int32_t* rays, const float* weights, int64_t N, int64_t M,
-                        float bound, const float* embeddings, const inr_grid_desc* desc /*host*/,
+                        float bound, const void* embeddings, const inr_grid_desc* desc /*host*/,
                         const float* packed /*device*/, int32_t K, float* extra_out, int32_t x_is_01,
                         uint64_t* cursors /*device [32], ZEROED BY THE CALLER: the launch's dynamic group schedule*/,
-                        inr_stream_t s);
-/* The same launch with upstream's `-O` numerics (opt-in: NeRFNetwork.half_table + mlp_fp16): embeddings_half is the fp16
- * copy of the instance table (T x 2 binary16), packed_f16 comes from inr_instance_pack_weights_f16 (same size and
- * fragment layout as inr_instance_pack_weights, fp16 values in the head slots); one fp16 MFMA pass per MLP GEMM.
- * Not available in the -DINR_MLP_FP32 build.                                                                      */
-int inr_instance_pack_weights_f16(const float* w0, const float* w1, const float* w2, int32_t K, float* packed /*host*/);
-int inr_instance_render_fast(const float* xyzs, const int32_t* rays, const float* weights, int64_t N, int64_t M,
-                             float bound, const void* embeddings_half, const inr_grid_desc* desc /*host*/,
-                             const float* packed_f16 /*device*/, int32_t K, float* extra_out, int32_t x_is_01,
-                             uint64_t* cursors /*device [32], zeroed by the caller*/, inr_stream_t s);
+                        int32_t numerics, inr_stream_t s);
 
 /* ---- weight gradient of the tiny bias-free MLP layers (replaces the BLAS call autograd makes for
  * nn.Linear in NeRFNetwork, a9/a13):  grad_w[o][i] += sum_m grad_y[m][o] * x[m][i],  n_in, n_out <= 64.

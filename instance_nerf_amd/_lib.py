@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("INR_LIB_PATH") or os.path.join(_HERE, "csrc", "libinr_hip.so")   # env override: profiling builds only
 MAX_LEVELS = 16
 GRID_FX_STATE_FLOATS = 4192      # include/inr.h INR_GRID_FX_STATE_FLOATS
+NUMERICS_TABLE_F16, NUMERICS_MLP_F16 = 1, 2      # include/inr.h INR_NUMERICS_*
 
 
 class GridDesc(Structure):
@@ -78,12 +79,9 @@ _SIGS = {
     "inr_finish_rays": (c_int32, [P, P, P, P, P, P, c_float, c_float, c_float, c_int64, P, P, P]),
     "inr_finish_rays_mse": (c_int32, [P, P, P, P, P, c_float, c_float, c_float, P, P, c_int64, P, P, P, P, P]),
     "inr_sh_table_q": (c_int32, [P, c_int64, P, P]),
-    "inr_nerf_forward_table": (c_int32, [P, P, P, c_int64, c_float, P, POINTER(GridDesc), P, c_float, P, P, P]),
-    "inr_nerf_forward_table_half": (c_int32, [P, P, P, c_int64, c_float, P, POINTER(GridDesc), P, c_float, P, P, P]),
-    "inr_nerf_forward_table_fast": (c_int32, [P, P, P, c_int64, c_float, P, c_int32, POINTER(GridDesc), P, c_float, P, P, P]),
+    "inr_nerf_forward_table": (c_int32, [P, P, P, c_int64, c_float, P, POINTER(GridDesc), P, c_float, P, P, c_int32, P]),
     "inr_nerf_forward_table_sliced_workspace_bytes": (c_int64, [c_int64]),
     "inr_nerf_forward_table_sliced": (c_int32, [P, P, P, c_int64, c_float, P, POINTER(GridDesc), P, c_float, P, P, P, P]),
-    "inr_nerf_pack_weights_f16": (c_int32, [P, P, P, P, P, P]),
     "inr_composite_rays_patch_forward": (c_int32, [P, P, P, P, c_int64, c_int64, c_float, P, c_int32, P, P, P, P, P, P, P]),
     "inr_project_masks_patch": (c_int32, [P, P, P, c_int64, c_int64, P, c_int32, c_int32, c_int32, P, c_int32, c_int32, c_int32,
                                           P, P]),
@@ -108,11 +106,10 @@ _SIGS = {
     "inr_sh_encode_forward": (c_int32, [P, c_int64, c_int32, P, P]),
     "inr_sh_encode_backward": (c_int32, [P, P, c_int64, c_int32, P, P]),
     "inr_nerf_packed_floats": (c_int64, []),
-    "inr_nerf_pack_weights": (c_int32, [P, P, P, P, P, P]),
+    "inr_nerf_pack_weights": (c_int32, [P, P, P, P, P, P, c_int32]),
     "inr_instance_packed_floats": (c_int64, [c_int32]),
-    "inr_instance_pack_weights": (c_int32, [P, P, P, c_int32, P]),
-    "inr_nerf_forward": (c_int32, [P, P, c_int64, P, c_float, P, POINTER(GridDesc), P, c_float, P, P, P, P]),
-    "inr_nerf_forward_fast": (c_int32, [P, P, c_int64, P, c_float, P, POINTER(GridDesc), P, c_float, P, P, P]),
+    "inr_instance_pack_weights": (c_int32, [P, P, P, c_int32, P, c_int32]),
+    "inr_nerf_forward": (c_int32, [P, P, c_int64, P, c_float, P, POINTER(GridDesc), P, c_float, P, P, P, c_int32, P]),
     "inr_nerf_forward_dirs": (c_int32, [P, c_int64, c_float, P, POINTER(GridDesc), P, P, c_int32, P, P]),
     "inr_nerf_forward_lattice": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_float, P, POINTER(GridDesc), P, P, c_int32,
                                            c_float, P, P]),
@@ -132,19 +129,16 @@ _SIGS = {
     "inr_roi_align_3d_backward_ws": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32,
                                                c_int32, c_int32, c_float, P, P, c_int64, P]),
     "inr_nerf_render": (c_int32, [P, P, P, P, c_int64, c_int64, c_float, P, POINTER(GridDesc), P, c_float, c_float,
-                                  P, P, P, P, P, c_int32, P]),
-    "inr_nerf_render_fast": (c_int32, [P, P, P, P, c_int64, c_int64, c_float, P, POINTER(GridDesc), P, c_float, c_float,
-                                  P, P, P, P, P, c_int32, P]),
-    "inr_instance_render": (c_int32, [P, P, P, c_int64, c_int64, c_float, P, POINTER(GridDesc), P, c_int32, P, c_int32, P, P]),
-    "inr_instance_render_fast": (c_int32, [P, P, P, c_int64, c_int64, c_float, P, POINTER(GridDesc), P, c_int32, P, c_int32, P, P]),
-    "inr_instance_pack_weights_f16": (c_int32, [P, P, P, c_int32, P]),
+                                  P, P, P, P, P, c_int32, c_int32, P]),
+    "inr_instance_render": (c_int32, [P, P, P, c_int64, c_int64, c_float, P, POINTER(GridDesc), P, c_int32, P, c_int32, P,
+                                      c_int32, P]),
     "inr_linear_wgrad_workspace_bytes": (c_int64, []),
     "inr_linear_wgrad": (c_int32, [P, P, c_int64, c_int32, c_int32, P, P, P]),
     "inr_adam_step": (c_int32, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_int32, c_float, P]),
 }
 EXPORTS = tuple(_SIGS)
 
-ABI_VERSION = 10         # include/inr.h INR_ABI_VERSION this binding was written against
+ABI_VERSION = 11         # include/inr.h INR_ABI_VERSION this binding was written against
 INSTANCE_STATS_WORKSPACE_BYTES = 512 * 64 * 8 * 4      # include/inr.h INR_INSTANCE_STATS_WORKSPACE_BYTES
 _lib = None
 

@@ -26,6 +26,7 @@
 // MFMA chain are explicit fmaf / MFMA.
 #include <atomic>
 #include <mutex>
+#include <type_traits>
 
 #include "common.h"
 #include "grid_common.h"
@@ -2635,6 +2636,102 @@ struct AttrOnce {
   }
 };
 
+// ---- host side of the field exports --------------------------------------------------------------------------------
+// Hash table of a field launch: its descriptor and its size in bytes as stored (fp32 [T,2], or the fp16 copy), which the
+// 32-bit gather offsets must be able to address.  `what` names the export in the error message.
+struct FieldTable {
+  GridDesc G;
+  const float2* emb;
+  uint32_t bytes;
+};
+static int field_table(const char* what, const inr_grid_desc* desc, const void* emb, bool half, FieldTable& t) {
+  if (int rc = make_grid_desc(desc, t.G)) return rc;
+  const uint64_t bytes = (uint64_t)desc->offsets[desc->num_levels] * (half ? 4ull : 8ull);
+  if (bytes >= (1ull << 31)) {
+    set_error("%s: table larger than 2 GiB is not addressable by the 32-bit gather offsets", what);
+    return INR_EINVAL;
+  }
+  t.emb = reinterpret_cast<const float2*>(emb);
+  t.bytes = (uint32_t)bytes;
+  return INR_OK;
+}
+static const float4* f4(const float* p) { return reinterpret_cast<const float4*>(p); }
+
+// Hybrid schedule (TileWalk) of one launch: frames and occupancy sweeps (four rounds of eight 1024-tile chunks and
+// more) draw their tiles through a cursor set zeroed on the launch's stream; smaller launches, and every launch inside a
+// stream capture (see steal_cursors), take the static deal (cursors() null).  finish() goes between the launch and its
+// check_launch, so that a failed event record surfaces in that export's return code.
+struct HybridSchedule {
+  StealSet set;
+  bool begin(hipStream_t s, int64_t n_tiles) {       // false: no cursor set (the error is set)
+    if ((n_tiles >> (kXcdChunkLog2 + 3)) < 4 || stream_is_capturing(s)) return true;
+    set = steal_cursors(s);
+    return set.cursors != nullptr;
+  }
+  unsigned long long* cursors() const { return set.cursors; }
+  void finish(hipStream_t s) { steal_release(set, s); }
+};
+
+// One field launch: the persistent grid of grid_for, kFieldThreads threads, `lds` bytes of dynamic LDS.
+template <typename Kern, typename... Args>
+static void launch_field(Kern kern, size_t lds, int64_t n_tiles, hipStream_t s, Args... args) {
+  kern<<<grid_for(kern, lds, n_tiles), kFieldThreads, lds, s>>>(args...);
+}
+
+// Runtime choices as compile-time constants, so that each launch is written once: with_kmt calls f with
+// std::integral_constant<int, K_MT> for the head's 16-row groups (1..3, 4 otherwise), with_flag with std::bool_constant.
+// with_mlp_f16 is with_flag for INR_NUMERICS_MLP_F16, whose kernels the exact-fp32 build does not have (check_numerics
+// refuses the bit there).
+template <typename F>
+static void with_kmt(int k_mt, F&& f) {
+  switch (k_mt) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    default: f(std::integral_constant<int, 4>{}); break;
+  }
+}
+template <typename F>
+static void with_flag(bool on, F&& f) {
+  if (on) f(std::true_type{});
+  else f(std::false_type{});
+}
+template <typename F>
+static void with_mlp_f16(bool on, F&& f) {
+#if !INR_MLP_FP32
+  if (on) return f(std::true_type{});
+#endif
+  f(std::false_type{});
+}
+
+// The `numerics` argument: a value whose bit is set in `accepted`.  Checked after an export's other arguments and its
+// table, so that each of those keeps the message of its own check.
+constexpr int kNumericsO = INR_NUMERICS_TABLE_F16 | INR_NUMERICS_MLP_F16;       // upstream's `-O`: both halves
+constexpr unsigned kAcceptPlainOrO = 1u | 1u << kNumericsO;
+constexpr unsigned kAcceptAny = 0xFu;
+constexpr unsigned kAcceptPack = 1u | 1u << INR_NUMERICS_MLP_F16;
+static int check_numerics(const char* what, int32_t numerics, unsigned accepted) {
+  if (numerics < 0 || numerics > 3 || !((accepted >> numerics) & 1u)) {
+    set_error("%s: numerics %d is not accepted here", what, numerics);
+    return INR_EINVAL;
+  }
+#if INR_MLP_FP32
+  if (numerics & INR_NUMERICS_MLP_F16) {
+    set_error("%s: INR_NUMERICS_MLP_F16 is not available in the exact-fp32 build", what);
+    return INR_EINVAL;
+  }
+#endif
+  return INR_OK;
+}
+
+// host packer of one weight section: the build's fragment values, or fp16 ones (INR_NUMERICS_MLP_F16)
+template <class KIdx>
+static void pack_section_as(int32_t numerics, float* dst, const float* W, int n_out, int n_in, int n_mt, int n_ks,
+                            KIdx kidx) {
+  if (numerics & INR_NUMERICS_MLP_F16) pack_section_f16(dst, W, n_out, n_in, n_mt, n_ks, kidx);
+  else pack_section(dst, W, n_out, n_in, n_mt, n_ks, kidx);
+}
+
 }  // namespace inr
 
 using namespace inr;
@@ -2644,24 +2741,14 @@ extern "C" {
 int64_t inr_nerf_packed_floats(void) { return kNerfFloats; }
 
 int inr_nerf_pack_weights(const float* sigma_w0, const float* sigma_w1, const float* color_w0, const float* color_w1,
-                          const float* color_w2, float* packed) {
+                          const float* color_w2, float* packed, int32_t numerics) {
   INR_REQUIRE(sigma_w0 && sigma_w1 && color_w0 && color_w1 && color_w2 && packed, "null pointer");
-  pack_section(packed + kSig0, sigma_w0, 64, 32, 4, 8, kidx_enc);
-  pack_section(packed + kSig1, sigma_w1, 16, 64, 1, 16, kidx_hidden);
-  pack_section(packed + kCol0, color_w0, 64, 31, 4, 8, kidx_color_in);
-  pack_section(packed + kCol1, color_w1, 64, 64, 4, 16, kidx_hidden);
-  pack_section(packed + kCol2, color_w2, 3, 64, 1, 16, kidx_hidden);
-  return INR_OK;
-}
-
-int inr_nerf_pack_weights_f16(const float* sigma_w0, const float* sigma_w1, const float* color_w0, const float* color_w1,
-                              const float* color_w2, float* packed) {
-  INR_REQUIRE(sigma_w0 && sigma_w1 && color_w0 && color_w1 && color_w2 && packed, "null pointer");
-  pack_section_f16(packed + kSig0, sigma_w0, 64, 32, 4, 8, kidx_enc);
-  pack_section_f16(packed + kSig1, sigma_w1, 16, 64, 1, 16, kidx_hidden);
-  pack_section_f16(packed + kCol0, color_w0, 64, 31, 4, 8, kidx_color_in);
-  pack_section_f16(packed + kCol1, color_w1, 64, 64, 4, 16, kidx_hidden);
-  pack_section_f16(packed + kCol2, color_w2, 3, 64, 1, 16, kidx_hidden);
+  if (int rc = check_numerics(__func__, numerics, kAcceptPack)) return rc;
+  pack_section_as(numerics, packed + kSig0, sigma_w0, 64, 32, 4, 8, kidx_enc);
+  pack_section_as(numerics, packed + kSig1, sigma_w1, 16, 64, 1, 16, kidx_hidden);
+  pack_section_as(numerics, packed + kCol0, color_w0, 64, 31, 4, 8, kidx_color_in);
+  pack_section_as(numerics, packed + kCol1, color_w1, 64, 64, 4, 16, kidx_hidden);
+  pack_section_as(numerics, packed + kCol2, color_w2, 3, 64, 1, 16, kidx_hidden);
   return INR_OK;
 }
 
@@ -2670,161 +2757,74 @@ int64_t inr_instance_packed_floats(int32_t K) {
   return kIns2 + K * 64;
 }
 
-int inr_instance_pack_weights(const float* w0, const float* w1, const float* w2, int32_t K, float* packed) {
+int inr_instance_pack_weights(const float* w0, const float* w1, const float* w2, int32_t K, float* packed,
+                              int32_t numerics) {
   INR_REQUIRE(w0 && w1 && w2 && packed, "null pointer");
   INR_REQUIRE(K > 0 && K <= 64 && K % 16 == 0, "K must be 16, 32, 48 or 64");
-  pack_section(packed + kIns0, w0, 64, 32, 4, 8, kidx_enc);
-  pack_section(packed + kIns1, w1, 64, 64, 4, 16, kidx_hidden);
-  pack_section(packed + kIns2, w2, K, 64, K / 16, 16, kidx_hidden);
+  if (int rc = check_numerics(__func__, numerics, kAcceptPack)) return rc;
+  pack_section_as(numerics, packed + kIns0, w0, 64, 32, 4, 8, kidx_enc);
+  pack_section_as(numerics, packed + kIns1, w1, 64, 64, 4, 16, kidx_hidden);
+  pack_section_as(numerics, packed + kIns2, w2, K, 64, K / 16, 16, kidx_hidden);
   return INR_OK;
 }
 
-int inr_nerf_forward_fast(const float* x, const float* d, int64_t M, const int32_t* n_samples_dev, float bound,
-                          const void* embeddings_half, const inr_grid_desc* desc, const float* packed_f16,
-                          float density_scale, float* sigma, float* rgb, inr_stream_t s) {
-#if INR_MLP_FP32
-  (void)x; (void)d; (void)M; (void)n_samples_dev; (void)bound; (void)embeddings_half; (void)desc; (void)packed_f16;
-  (void)density_scale; (void)sigma; (void)rgb; (void)s;
-  set_error("nerf_forward_fast: not available in the exact-fp32 build");
-  return INR_EINVAL;
-#else
-  INR_REQUIRE(M >= 0 && desc, "bad argument");
-  if (M == 0) return INR_OK;
-  INR_REQUIRE(x && d && embeddings_half && packed_f16 && sigma && rgb, "null pointer");
-  INR_REQUIRE(((uintptr_t)embeddings_half & 3) == 0 && ((uintptr_t)packed_f16 & 15) == 0, "embeddings/packed misaligned");
-  GridDesc G;
-  int rc = make_grid_desc(desc, G);
-  if (rc) return rc;
-  const uint64_t emb_bytes64 = (uint64_t)desc->offsets[desc->num_levels] * 4ull;
-  INR_REQUIRE(emb_bytes64 < (1ull << 31), "table larger than 2 GiB is not addressable by the 32-bit gather offsets");
-  const size_t lds = kNerfFloats * sizeof(float) + kLevelRecBytes;
-  const int grid = grid_for(k_nerf_fwd<true, false, 0, true, true>, lds, (M + 15) / 16);
-  k_nerf_fwd<true, false, 0, true, true><<<grid, kFieldThreads, lds, as_stream(s)>>>(
-      x, d, M, n_samples_dev, bound, reinterpret_cast<const float2*>(embeddings_half), (uint32_t)emb_bytes64, G,
-      reinterpret_cast<const float4*>(packed_f16), density_scale, sigma, rgb, nullptr, nullptr, nullptr, NerfSave{}, nullptr);
-  return check_launch("nerf_forward_fast");
-#endif
-}
-
 int inr_nerf_forward(const float* x, const float* d, int64_t M, const int32_t* n_samples_dev, float bound,
-                     const float* embeddings, const inr_grid_desc* desc, const float* packed, float density_scale,
-                     float* sigma, float* rgb, float* geo_feat, inr_stream_t s) {
+                     const void* embeddings, const inr_grid_desc* desc, const float* packed, float density_scale,
+                     float* sigma, float* rgb, float* geo_feat, int32_t numerics, inr_stream_t s) {
+  const bool o = numerics == kNumericsO;
   INR_REQUIRE(M >= 0 && desc, "bad argument");
   if (M == 0) return INR_OK;
-  INR_REQUIRE(x && embeddings && packed && sigma, "null pointer");
+  INR_REQUIRE(x && embeddings && packed && sigma && (rgb || !o), "null pointer");
   INR_REQUIRE(!rgb || d, "rgb requested without view directions");
-  INR_REQUIRE(((uintptr_t)embeddings & 7) == 0 && ((uintptr_t)packed & 15) == 0, "embeddings/packed misaligned");
-  GridDesc G;
-  int rc = make_grid_desc(desc, G);
-  if (rc) return rc;
-  if (M == 0) return INR_OK;
-  const float2* e = reinterpret_cast<const float2*>(embeddings);
-  const float4* p = reinterpret_cast<const float4*>(packed);
-  const uint64_t emb_bytes64 = (uint64_t)desc->offsets[desc->num_levels] * 8ull;
-  INR_REQUIRE(emb_bytes64 < (1ull << 31), "table larger than 2 GiB is not addressable by the 32-bit gather offsets");
-  const uint32_t emb_bytes = (uint32_t)emb_bytes64;
+  INR_REQUIRE(!(o && geo_feat), "no geo_feat under the -O numerics");
+  INR_REQUIRE(((uintptr_t)embeddings & (o ? 3 : 7)) == 0 && ((uintptr_t)packed & 15) == 0, "embeddings/packed misaligned");
+  FieldTable t;
+  if (int rc = field_table(__func__, desc, embeddings, o, t)) return rc;
+  if (int rc = check_numerics(__func__, numerics, kAcceptPlainOrO)) return rc;
   const int64_t n_tiles = (M + 15) / 16;
-  // frames and occupancy sweeps (four rounds of eight 1024-tile chunks and more): hybrid schedule, see TileWalk
-  StealSet steal_set;
-  if ((n_tiles >> (kXcdChunkLog2 + 3)) >= 4 && !stream_is_capturing(as_stream(s))) {   // captured: static deal, see steal_cursors
-    steal_set = steal_cursors(as_stream(s));
-    if (!steal_set.cursors) return INR_ELAUNCH;
-  }
-  unsigned long long* steal = steal_set.cursors;
-  if (rgb) {
-    const size_t lds = kNerfFloats * sizeof(float) + kLevelRecBytes;
-    const int grid = grid_for(k_nerf_fwd<true>, lds, n_tiles);
-    k_nerf_fwd<true><<<grid, kFieldThreads, lds, as_stream(s)>>>(x, d, M, n_samples_dev, bound, e, emb_bytes, G, p,
-                                                      density_scale, sigma, rgb, geo_feat, nullptr, nullptr, NerfSave{}, steal);
-  } else {
-    const size_t lds = kCol0 * sizeof(float) + kLevelRecBytes;
-    const int grid = grid_for(k_nerf_fwd<false>, lds, n_tiles);
-    k_nerf_fwd<false><<<grid, kFieldThreads, lds, as_stream(s)>>>(x, d, M, n_samples_dev, bound, e, emb_bytes, G, p,
-                                                       density_scale, sigma, nullptr, geo_feat, nullptr, nullptr, NerfSave{}, steal);
-  }
-  steal_release(steal_set, as_stream(s));
+  const hipStream_t st = as_stream(s);
+  // frames and occupancy sweeps take the hybrid schedule; the -O launch (the frozen NeRF of the instance stage) does not
+  HybridSchedule hybrid;
+  if (!o && !hybrid.begin(st, n_tiles)) return INR_ELAUNCH;
+  const size_t lds = (rgb ? kNerfFloats : kCol0) * sizeof(float) + kLevelRecBytes;
+  const auto launch = [&](auto kern) {
+    launch_field(kern, lds, n_tiles, st, x, d, M, n_samples_dev, bound, t.emb, t.bytes, t.G, f4(packed), density_scale,
+                 sigma, rgb, geo_feat, nullptr, nullptr, NerfSave{}, hybrid.cursors());
+  };
+  with_mlp_f16(o, [&](auto fast) {
+    if constexpr (decltype(fast)::value) launch(k_nerf_fwd<true, false, 0, true, true>);
+    else if (rgb) launch(k_nerf_fwd<true>);
+    else launch(k_nerf_fwd<false>);
+  });
+  hybrid.finish(st);
   return check_launch("nerf_forward");
 }
 
-static int nerf_forward_table_impl(const float* x01, const int32_t* ray_ids, const float* sh_table_q, int64_t M, float bound,
-                                   const void* embeddings, bool half, bool fast, const inr_grid_desc* desc,
-                                   const float* packed, float density_scale, float* sigma, float* rgb, inr_stream_t s);
-
 int inr_nerf_forward_table(const float* x01, const int32_t* ray_ids, const float* sh_table_q, int64_t M, float bound,
-                           const float* embeddings, const inr_grid_desc* desc, const float* packed, float density_scale,
-                           float* sigma, float* rgb, inr_stream_t s) {
-  return nerf_forward_table_impl(x01, ray_ids, sh_table_q, M, bound, embeddings, false, false, desc, packed, density_scale,
-                                 sigma, rgb, s);
-}
-
-int inr_nerf_forward_table_half(const float* x01, const int32_t* ray_ids, const float* sh_table_q, int64_t M, float bound,
-                                const void* embeddings_half, const inr_grid_desc* desc, const float* packed,
-                                float density_scale, float* sigma, float* rgb, inr_stream_t s) {
-  return nerf_forward_table_impl(x01, ray_ids, sh_table_q, M, bound, embeddings_half, true, false, desc, packed,
-                                 density_scale, sigma, rgb, s);
-}
-
-int inr_nerf_forward_table_fast(const float* x01, const int32_t* ray_ids, const float* sh_table_q, int64_t M, float bound,
-                                const void* embeddings, int32_t table_is_half, const inr_grid_desc* desc,
-                                const float* packed, float density_scale, float* sigma, float* rgb, inr_stream_t s) {
-#if INR_MLP_FP32
-  (void)x01; (void)ray_ids; (void)sh_table_q; (void)M; (void)bound; (void)embeddings; (void)table_is_half; (void)desc;
-  (void)packed; (void)density_scale; (void)sigma; (void)rgb; (void)s;
-  set_error("nerf_forward_table_fast: not available in the exact-fp32 build");
-  return INR_EINVAL;
-#else
-  return nerf_forward_table_impl(x01, ray_ids, sh_table_q, M, bound, embeddings, table_is_half != 0, true, desc, packed,
-                                 density_scale, sigma, rgb, s);
-#endif
-}
-
-extern "C++" {
-template <bool kHalf, bool kFast>
-static int launch_nerf_table(const float* x01, const int32_t* ray_ids, const float* sh_table_q, int64_t M, float bound,
-                             const void* embeddings, uint32_t emb_bytes, const GridDesc& G, const float* packed,
-                             float density_scale, float* sigma, float* rgb, size_t lds, inr_stream_t s) {
-  const int grid = grid_for(k_nerf_fwd<true, true, 0, kHalf, kFast>, lds, (M + 15) / 16);
-  // frames (four rounds of eight 1024-tile chunks and more) take the hybrid schedule: its cursors, zeroed on this stream
-  StealSet steal_set;
-  if ((((M + 15) / 16) >> (kXcdChunkLog2 + 3)) >= 4 && !stream_is_capturing(as_stream(s))) {
-    steal_set = steal_cursors(as_stream(s));
-    if (!steal_set.cursors) return INR_ELAUNCH;
-  }
-  unsigned long long* steal = steal_set.cursors;
-  k_nerf_fwd<true, true, 0, kHalf, kFast><<<grid, kFieldThreads, lds, as_stream(s)>>>(
-      x01, nullptr, M, nullptr, bound, reinterpret_cast<const float2*>(embeddings), emb_bytes, G,
-      reinterpret_cast<const float4*>(packed), density_scale, sigma, rgb, nullptr, ray_ids,
-      reinterpret_cast<const float4*>(sh_table_q), NerfSave{}, steal);
-  steal_release(steal_set, as_stream(s));
-  return check_launch("nerf_forward_table");
-}
-}  // extern "C++"
-
-static int nerf_forward_table_impl(const float* x01, const int32_t* ray_ids, const float* sh_table_q, int64_t M, float bound,
-                                   const void* embeddings, bool half, bool fast, const inr_grid_desc* desc,
-                                   const float* packed, float density_scale, float* sigma, float* rgb, inr_stream_t s) {
+                           const void* embeddings, const inr_grid_desc* desc, const float* packed, float density_scale,
+                           float* sigma, float* rgb, int32_t numerics, inr_stream_t s) {
   INR_REQUIRE(M >= 0 && desc, "bad argument");
   if (M == 0) return INR_OK;
   INR_REQUIRE(x01 && ray_ids && sh_table_q && embeddings && packed && sigma && rgb, "null pointer");
   INR_REQUIRE(((uintptr_t)embeddings & 7) == 0 && ((uintptr_t)packed & 15) == 0 && ((uintptr_t)sh_table_q & 15) == 0,
               "embeddings/packed/sh_table_q misaligned");
-  GridDesc G;
-  int rc = make_grid_desc(desc, G);
-  if (rc) return rc;
-  const uint64_t emb_bytes64 = (uint64_t)desc->offsets[desc->num_levels] * 8ull;
-  INR_REQUIRE(emb_bytes64 < (1ull << 31), "table larger than 2 GiB is not addressable by the 32-bit gather offsets");
+  FieldTable t;
+  if (int rc = field_table(__func__, desc, embeddings, numerics & INR_NUMERICS_TABLE_F16, t)) return rc;
+  if (int rc = check_numerics(__func__, numerics, kAcceptAny)) return rc;
   const size_t lds = std::max(kNerfFloats * sizeof(float) + kLevelRecBytes, (size_t)g_field_lds_min);
-  const uint32_t eb = (uint32_t)(half ? emb_bytes64 / 2 : emb_bytes64);
-#define INR_TABLE_LAUNCH(H, F) \
-  launch_nerf_table<H, F>(x01, ray_ids, sh_table_q, M, bound, embeddings, eb, G, packed, density_scale, sigma, rgb, lds, s)
-#if INR_MLP_FP32
-  (void)fast;
-  return half ? INR_TABLE_LAUNCH(true, false) : INR_TABLE_LAUNCH(false, false);
-#else
-  if (fast) return half ? INR_TABLE_LAUNCH(true, true) : INR_TABLE_LAUNCH(false, true);
-  return half ? INR_TABLE_LAUNCH(true, false) : INR_TABLE_LAUNCH(false, false);
-#endif
-#undef INR_TABLE_LAUNCH
+  const int64_t n_tiles = (M + 15) / 16;
+  const hipStream_t st = as_stream(s);
+  HybridSchedule hybrid;         // frames (four rounds of eight 1024-tile chunks and more)
+  if (!hybrid.begin(st, n_tiles)) return INR_ELAUNCH;
+  with_flag(numerics & INR_NUMERICS_TABLE_F16, [&](auto half) {
+    with_mlp_f16(numerics & INR_NUMERICS_MLP_F16, [&](auto fast) {
+      launch_field(k_nerf_fwd<true, true, 0, decltype(half)::value, decltype(fast)::value>, lds, n_tiles, st, x01,
+                   nullptr, M, nullptr, bound, t.emb, t.bytes, t.G, f4(packed), density_scale, sigma, rgb, nullptr,
+                   ray_ids, f4(sh_table_q), NerfSave{}, hybrid.cursors());
+    });
+  });
+  hybrid.finish(st);
+  return check_launch("nerf_forward_table");
 }
 
 // ---- sliced frame path: level-major pre-pass over the three finest levels + fused kernel on the other thirteen ------
@@ -2842,13 +2842,8 @@ int inr_nerf_forward_table_sliced(const float* x01, const int32_t* ray_ids, cons
               ((uintptr_t)fine_ws & 7) == 0, "embeddings/packed/sh_table_q/fine_ws misaligned");
   INR_REQUIRE(desc->num_levels == 16, "the sliced frame path needs the 16-level table");
   for (int l = 8; l < 16; ++l) INR_REQUIRE(desc->hashed[l], "the sliced frame path needs hashed fine levels (8..15)");
-  GridDesc G;
-  int rc = make_grid_desc(desc, G);
-  if (rc) return rc;
-  const uint64_t emb_bytes64 = (uint64_t)desc->offsets[desc->num_levels] * 8ull;
-  INR_REQUIRE(emb_bytes64 < (1ull << 31), "table larger than 2 GiB is not addressable by the 32-bit gather offsets");
-  const uint32_t eb = (uint32_t)emb_bytes64;
-  const float2* e = reinterpret_cast<const float2*>(embeddings);
+  FieldTable t;
+  if (int rc = field_table(__func__, desc, embeddings, false, t)) return rc;
   const size_t lds = std::max(kNerfFloats * sizeof(float) + kLevelRecBytes, (size_t)g_field_lds_min);
   hipStream_t st = as_stream(s);
   static int fit = 0;                      // resident pre-pass workgroups per CU (a constant of the build)
@@ -2860,17 +2855,13 @@ int inr_nerf_forward_table_sliced(const float* x01, const int32_t* ray_ids, cons
   //  27.3-27.9 ms against 27.5 ms one after the other, 4.2-4.4 against 4.07 ms with growing steps.)
   const int64_t per_wg = 32 * kSliceTilesPerIter * (kSliceThreads / 64);
   const int gx = (int)std::max<int64_t>(1, std::min<int64_t>((M + per_wg - 1) / per_wg, (int64_t)cu_count() * fit));
-  k_grid_fine_slices<<<dim3(gx, kSliceLevels), kSliceThreads, 0, st>>>(x01, M, e, eb, G, fine_ws);
-  const int grid = grid_for(k_nerf_fwd<true, true, 0, false, false, true>, lds, (M + 15) / 16);
-  StealSet steal_set;
-  if ((((M + 15) / 16) >> (kXcdChunkLog2 + 3)) >= 4 && !stream_is_capturing(st)) {
-    steal_set = steal_cursors(st);
-    if (!steal_set.cursors) return INR_ELAUNCH;
-  }
-  k_nerf_fwd<true, true, 0, false, false, true><<<grid, kFieldThreads, lds, st>>>(
-      x01, fine_ws, M, nullptr, bound, e, eb, G, reinterpret_cast<const float4*>(packed), density_scale, sigma, rgb, nullptr,
-      ray_ids, reinterpret_cast<const float4*>(sh_table_q), NerfSave{}, steal_set.cursors);
-  steal_release(steal_set, st);
+  k_grid_fine_slices<<<dim3(gx, kSliceLevels), kSliceThreads, 0, st>>>(x01, M, t.emb, t.bytes, t.G, fine_ws);
+  HybridSchedule hybrid;
+  if (!hybrid.begin(st, (M + 15) / 16)) return INR_ELAUNCH;
+  launch_field(k_nerf_fwd<true, true, 0, false, false, true>, lds, (M + 15) / 16, st, x01, fine_ws, M, nullptr, bound,
+               t.emb, t.bytes, t.G, f4(packed), density_scale, sigma, rgb, nullptr, ray_ids, f4(sh_table_q), NerfSave{},
+               hybrid.cursors());
+  hybrid.finish(st);
   return check_launch("nerf_forward_table_sliced");
 }
 
@@ -2882,16 +2873,11 @@ int inr_nerf_forward_dirs(const float* x, int64_t M, float bound, const float* e
   INR_REQUIRE(n_dirs >= 1 && n_dirs <= kMaxExtractDirs, "1..8 view directions");
   INR_REQUIRE(((uintptr_t)embeddings & 7) == 0 && ((uintptr_t)packed & 15) == 0 && ((uintptr_t)out & 15) == 0,
               "embeddings/packed/out misaligned");
-  GridDesc G;
-  int rc = make_grid_desc(desc, G);
-  if (rc) return rc;
-  const uint64_t emb_bytes64 = (uint64_t)desc->offsets[desc->num_levels] * 8ull;
-  INR_REQUIRE(emb_bytes64 < (1ull << 31), "table larger than 2 GiB is not addressable by the 32-bit gather offsets");
+  FieldTable t;
+  if (int rc = field_table(__func__, desc, embeddings, false, t)) return rc;
   const size_t lds = kNerfFloats * sizeof(float) + kLevelRecBytes + kMaxExtractDirs * 16 * sizeof(float);
-  const int grid = grid_for(k_nerf_fwd_dirs<false>, lds, (M + 15) / 16);
-  k_nerf_fwd_dirs<false><<<grid, kFieldThreads, lds, as_stream(s)>>>(
-      x, M, bound, reinterpret_cast<const float2*>(embeddings), (uint32_t)emb_bytes64, G,
-      reinterpret_cast<const float4*>(packed), sh_dirs, n_dirs, reinterpret_cast<float4*>(out), LatticeDesc{}, -INFINITY);
+  launch_field(k_nerf_fwd_dirs<false>, lds, (M + 15) / 16, as_stream(s), x, M, bound, t.emb, t.bytes, t.G, f4(packed),
+               sh_dirs, n_dirs, reinterpret_cast<float4*>(out), LatticeDesc{}, -INFINITY);
   return check_launch("nerf_forward_dirs");
 }
 
@@ -2904,18 +2890,13 @@ int inr_nerf_forward_lattice(const float* ax_w, const float* ax_l, const float* 
   INR_REQUIRE(n_dirs >= 1 && n_dirs <= kMaxExtractDirs, "1..8 view directions");
   INR_REQUIRE(((uintptr_t)embeddings & 7) == 0 && ((uintptr_t)packed & 15) == 0 && ((uintptr_t)out & 15) == 0,
               "embeddings/packed/out misaligned");
-  GridDesc G;
-  int rc = make_grid_desc(desc, G);
-  if (rc) return rc;
-  const uint64_t emb_bytes64 = (uint64_t)desc->offsets[desc->num_levels] * 8ull;
-  INR_REQUIRE(emb_bytes64 < (1ull << 31), "table larger than 2 GiB is not addressable by the 32-bit gather offsets");
+  FieldTable t;
+  if (int rc = field_table(__func__, desc, embeddings, false, t)) return rc;
   LatticeDesc lat{ax_w, ax_l, ax_h, W, L, H, (W + 15) / 16 * 16};
   const int64_t M = (int64_t)lat.Wp * L * H;           // traversal length: runs of 16 along w, padded per (il, ih)
   const size_t lds = kNerfFloats * sizeof(float) + kLevelRecBytes + kMaxExtractDirs * 16 * sizeof(float);
-  const int grid = grid_for(k_nerf_fwd_dirs<true>, lds, (M + 15) / 16);
-  k_nerf_fwd_dirs<true><<<grid, kFieldThreads, lds, as_stream(s)>>>(
-      nullptr, M, bound, reinterpret_cast<const float2*>(embeddings), (uint32_t)emb_bytes64, G,
-      reinterpret_cast<const float4*>(packed), sh_dirs, n_dirs, reinterpret_cast<float4*>(out), lat, logit_min);
+  launch_field(k_nerf_fwd_dirs<true>, lds, (M + 15) / 16, as_stream(s), nullptr, M, bound, t.emb, t.bytes, t.G,
+               f4(packed), sh_dirs, n_dirs, reinterpret_cast<float4*>(out), lat, logit_min);
   return check_launch("nerf_forward_lattice");
 }
 
@@ -2927,24 +2908,13 @@ int inr_instance_forward(const float* x, int64_t M, const int32_t* n_samples_dev
   INR_REQUIRE(K > 0 && K <= 64 && K % 16 == 0, "K must be 16, 32, 48 or 64");
   INR_REQUIRE(((uintptr_t)embeddings & 7) == 0 && ((uintptr_t)packed & 15) == 0 && ((uintptr_t)logits & 15) == 0,
               "embeddings/packed/logits misaligned");
-  GridDesc G;
-  int rc = make_grid_desc(desc, G);
-  if (rc) return rc;
-  if (M == 0) return INR_OK;
-  const float2* e = reinterpret_cast<const float2*>(embeddings);
-  const float4* p = reinterpret_cast<const float4*>(packed);
-  const uint64_t emb_bytes64 = (uint64_t)desc->offsets[desc->num_levels] * 8ull;
-  INR_REQUIRE(emb_bytes64 < (1ull << 31), "table larger than 2 GiB is not addressable by the 32-bit gather offsets");
-  const uint32_t eb = (uint32_t)emb_bytes64;
+  FieldTable t;
+  if (int rc = field_table(__func__, desc, embeddings, false, t)) return rc;
   const size_t lds = (size_t)(kIns2 + K * 64) * sizeof(float) + kLevelRecBytes;
-  const int64_t n_tiles = (M + 15) / 16;
-  hipStream_t st = as_stream(s);
-  switch (K / 16) {
-    case 1: k_instance_fwd<1><<<grid_for(k_instance_fwd<1>, lds, n_tiles), kFieldThreads, lds, st>>>(x, M, n_samples_dev, bound, e, eb, G, p, logits, nullptr, nullptr, nullptr); break;
-    case 2: k_instance_fwd<2><<<grid_for(k_instance_fwd<2>, lds, n_tiles), kFieldThreads, lds, st>>>(x, M, n_samples_dev, bound, e, eb, G, p, logits, nullptr, nullptr, nullptr); break;
-    case 3: k_instance_fwd<3><<<grid_for(k_instance_fwd<3>, lds, n_tiles), kFieldThreads, lds, st>>>(x, M, n_samples_dev, bound, e, eb, G, p, logits, nullptr, nullptr, nullptr); break;
-    default: k_instance_fwd<4><<<grid_for(k_instance_fwd<4>, lds, n_tiles), kFieldThreads, lds, st>>>(x, M, n_samples_dev, bound, e, eb, G, p, logits, nullptr, nullptr, nullptr); break;
-  }
+  with_kmt(K / 16, [&](auto kmt) {
+    launch_field(k_instance_fwd<decltype(kmt)::value>, lds, (M + 15) / 16, as_stream(s), x, M, n_samples_dev, bound,
+                 t.emb, t.bytes, t.G, f4(packed), logits, nullptr, nullptr, nullptr);
+  });
   return check_launch("instance_forward");
 }
 
@@ -2977,23 +2947,13 @@ int inr_instance_forward_train(const float* x, int64_t M, float bound, const flo
   INR_REQUIRE(((uintptr_t)embeddings & 7) == 0 &&
                   (((uintptr_t)packed | (uintptr_t)logits | (uintptr_t)enc | (uintptr_t)h1 | (uintptr_t)h2) & 15) == 0,
               "embeddings/packed/outputs misaligned");
-  GridDesc G;
-  int rc = make_grid_desc(desc, G);
-  if (rc) return rc;
-  const float2* e = reinterpret_cast<const float2*>(embeddings);
-  const float4* p = reinterpret_cast<const float4*>(packed);
-  const uint64_t emb_bytes64 = (uint64_t)desc->offsets[desc->num_levels] * 8ull;
-  INR_REQUIRE(emb_bytes64 < (1ull << 31), "table larger than 2 GiB is not addressable by the 32-bit gather offsets");
-  const uint32_t eb = (uint32_t)emb_bytes64;
+  FieldTable t;
+  if (int rc = field_table(__func__, desc, embeddings, false, t)) return rc;
   const size_t lds = (size_t)(kIns2 + K * 64) * sizeof(float) + kLevelRecBytes;
-  const int64_t n_tiles = (M + 15) / 16;
-  hipStream_t st = as_stream(s);
-  switch (K / 16) {
-    case 1: k_instance_fwd<1, 1><<<grid_for(k_instance_fwd<1, 1>, lds, n_tiles), kFieldThreads, lds, st>>>(x, M, nullptr, bound, e, eb, G, p, logits, enc, h1, h2); break;
-    case 2: k_instance_fwd<2, 1><<<grid_for(k_instance_fwd<2, 1>, lds, n_tiles), kFieldThreads, lds, st>>>(x, M, nullptr, bound, e, eb, G, p, logits, enc, h1, h2); break;
-    case 3: k_instance_fwd<3, 1><<<grid_for(k_instance_fwd<3, 1>, lds, n_tiles), kFieldThreads, lds, st>>>(x, M, nullptr, bound, e, eb, G, p, logits, enc, h1, h2); break;
-    default: k_instance_fwd<4, 1><<<grid_for(k_instance_fwd<4, 1>, lds, n_tiles), kFieldThreads, lds, st>>>(x, M, nullptr, bound, e, eb, G, p, logits, enc, h1, h2); break;
-  }
+  with_kmt(K / 16, [&](auto kmt) {
+    launch_field(k_instance_fwd<decltype(kmt)::value, 1>, lds, (M + 15) / 16, as_stream(s), x, M, nullptr, bound, t.emb,
+                 t.bytes, t.G, f4(packed), logits, enc, h1, h2);
+  });
   return check_launch("instance_forward_train");
 }
 
@@ -3006,23 +2966,13 @@ int inr_instance_forward_enc(const float* x, int64_t M, const int32_t* n_samples
   INR_REQUIRE(K > 0 && K <= 64 && K % 16 == 0, "K must be 16, 32, 48 or 64");
   INR_REQUIRE(((uintptr_t)embeddings & 7) == 0 && (((uintptr_t)packed | (uintptr_t)logits | (uintptr_t)enc) & 15) == 0,
               "embeddings/packed/outputs misaligned");
-  GridDesc G;
-  int rc = make_grid_desc(desc, G);
-  if (rc) return rc;
-  const float2* e = reinterpret_cast<const float2*>(embeddings);
-  const float4* p = reinterpret_cast<const float4*>(packed);
-  const uint64_t emb_bytes64 = (uint64_t)desc->offsets[desc->num_levels] * 8ull;
-  INR_REQUIRE(emb_bytes64 < (1ull << 31), "table larger than 2 GiB is not addressable by the 32-bit gather offsets");
-  const uint32_t eb = (uint32_t)emb_bytes64;
+  FieldTable t;
+  if (int rc = field_table(__func__, desc, embeddings, false, t)) return rc;
   const size_t lds = (size_t)(kIns2 + K * 64) * sizeof(float) + kLevelRecBytes;
-  const int64_t n_tiles = (M + 15) / 16;
-  hipStream_t st = as_stream(s);
-  switch (K / 16) {
-    case 1: k_instance_fwd<1, 2><<<grid_for(k_instance_fwd<1, 2>, lds, n_tiles), kFieldThreads, lds, st>>>(x, M, n_samples_dev, bound, e, eb, G, p, logits, enc, nullptr, nullptr); break;
-    case 2: k_instance_fwd<2, 2><<<grid_for(k_instance_fwd<2, 2>, lds, n_tiles), kFieldThreads, lds, st>>>(x, M, n_samples_dev, bound, e, eb, G, p, logits, enc, nullptr, nullptr); break;
-    case 3: k_instance_fwd<3, 2><<<grid_for(k_instance_fwd<3, 2>, lds, n_tiles), kFieldThreads, lds, st>>>(x, M, n_samples_dev, bound, e, eb, G, p, logits, enc, nullptr, nullptr); break;
-    default: k_instance_fwd<4, 2><<<grid_for(k_instance_fwd<4, 2>, lds, n_tiles), kFieldThreads, lds, st>>>(x, M, n_samples_dev, bound, e, eb, G, p, logits, enc, nullptr, nullptr); break;
-  }
+  with_kmt(K / 16, [&](auto kmt) {
+    launch_field(k_instance_fwd<decltype(kmt)::value, 2>, lds, (M + 15) / 16, as_stream(s), x, M, n_samples_dev, bound,
+                 t.emb, t.bytes, t.G, f4(packed), logits, enc, nullptr, nullptr);
+  });
   return check_launch("instance_forward_enc");
 }
 
@@ -3058,20 +3008,11 @@ int inr_instance_lattice(const float* ax_w, const float* ax_l, const float* ax_h
   const int64_t n_tiles = (int64_t)lat.Wp * L * H / 16;
   const float2* en = reinterpret_cast<const float2*>(nerf_embeddings);
   const float2* ei = reinterpret_cast<const float2*>(inst_embeddings);
-  const float4* pn = reinterpret_cast<const float4*>(nerf_packed);
-  const float4* pk = reinterpret_cast<const float4*>(inst_packed);
-  hipStream_t st = as_stream(s);
-#define INR_IL_LAUNCH(KMT)                                                                                              \
-  k_instance_lattice<KMT><<<grid_for(k_instance_lattice<KMT>, lds, n_tiles), kFieldThreads, lds, st>>>(                 \
-      lat, bound, en, (uint32_t)bn, Gn, pn, density_scale, sigma_thresh, ei, (uint32_t)bi, Gi, pk, K, labels, confidence, \
-      density_logit)
-  switch (K_MT) {
-    case 1: INR_IL_LAUNCH(1); break;
-    case 2: INR_IL_LAUNCH(2); break;
-    case 3: INR_IL_LAUNCH(3); break;
-    default: INR_IL_LAUNCH(4); break;
-  }
-#undef INR_IL_LAUNCH
+  with_kmt(K_MT, [&](auto kmt) {
+    launch_field(k_instance_lattice<decltype(kmt)::value>, lds, n_tiles, as_stream(s), lat, bound, en, (uint32_t)bn, Gn,
+                 f4(nerf_packed), density_scale, sigma_thresh, ei, (uint32_t)bi, Gi, f4(inst_packed), K, labels,
+                 confidence, density_logit);
+  });
   return check_launch("instance_lattice");
 }
 
@@ -3181,17 +3122,11 @@ int inr_nerf_forward_train(const float* x, const float* d, int64_t M, float boun
   INR_REQUIRE(((uintptr_t)embeddings & 7) == 0 &&
                   (((uintptr_t)packed | (uintptr_t)enc | (uintptr_t)h1 | (uintptr_t)so | (uintptr_t)cin | (uintptr_t)c1 |
                     (uintptr_t)c2) & 15) == 0, "embeddings/packed/activation arrays misaligned");
-  GridDesc G;
-  int rc = make_grid_desc(desc, G);
-  if (rc) return rc;
-  const uint64_t emb_bytes64 = (uint64_t)desc->offsets[desc->num_levels] * 8ull;
-  INR_REQUIRE(emb_bytes64 < (1ull << 31), "table larger than 2 GiB is not addressable by the 32-bit gather offsets");
+  FieldTable t;
+  if (int rc = field_table(__func__, desc, embeddings, false, t)) return rc;
   const size_t lds = kNerfFloats * sizeof(float) + kLevelRecBytes;
-  const int grid = grid_for(k_nerf_fwd<true, false, 1>, lds, (M + 15) / 16);
-  k_nerf_fwd<true, false, 1><<<grid, kFieldThreads, lds, as_stream(s)>>>(
-      x, d, M, nullptr, bound, reinterpret_cast<const float2*>(embeddings), (uint32_t)emb_bytes64, G,
-      reinterpret_cast<const float4*>(packed), 1.0f, sigma, rgb, nullptr, nullptr, nullptr,
-      NerfSave{enc, h1, so, cin, c1, c2}, nullptr);
+  launch_field(k_nerf_fwd<true, false, 1>, lds, (M + 15) / 16, as_stream(s), x, d, M, nullptr, bound, t.emb, t.bytes,
+               t.G, f4(packed), 1.0f, sigma, rgb, nullptr, nullptr, nullptr, NerfSave{enc, h1, so, cin, c1, c2}, nullptr);
   return check_launch("nerf_forward_train");
 }
 
@@ -3202,18 +3137,13 @@ int inr_nerf_forward_enc(const float* x, const float* d, int64_t M, float bound,
   INR_REQUIRE(x && d && embeddings && packed && sigma && rgb && enc, "null pointer");
   INR_REQUIRE(((uintptr_t)embeddings & 7) == 0 && (((uintptr_t)packed | (uintptr_t)enc) & 15) == 0,
               "embeddings/packed/enc misaligned");
-  GridDesc G;
-  int rc = make_grid_desc(desc, G);
-  if (rc) return rc;
-  const uint64_t emb_bytes64 = (uint64_t)desc->offsets[desc->num_levels] * 8ull;
-  INR_REQUIRE(emb_bytes64 < (1ull << 31), "table larger than 2 GiB is not addressable by the 32-bit gather offsets");
+  FieldTable t;
+  if (int rc = field_table(__func__, desc, embeddings, false, t)) return rc;
   const size_t lds = kNerfFloats * sizeof(float) + kLevelRecBytes;
-  const int grid = grid_for(k_nerf_fwd<true, false, 2>, lds, (M + 15) / 16);
   NerfSave sv{};
   sv.enc = enc;
-  k_nerf_fwd<true, false, 2><<<grid, kFieldThreads, lds, as_stream(s)>>>(
-      x, d, M, nullptr, bound, reinterpret_cast<const float2*>(embeddings), (uint32_t)emb_bytes64, G,
-      reinterpret_cast<const float4*>(packed), 1.0f, sigma, rgb, nullptr, nullptr, nullptr, sv, nullptr);
+  launch_field(k_nerf_fwd<true, false, 2>, lds, (M + 15) / 16, as_stream(s), x, d, M, nullptr, bound, t.emb, t.bytes,
+               t.G, f4(packed), 1.0f, sigma, rgb, nullptr, nullptr, nullptr, sv, nullptr);
   return check_launch("nerf_forward_enc");
 }
 
@@ -3262,45 +3192,10 @@ int inr_nerf_backward(const float* grad_sigma, const float* grad_rgb, const floa
   return check_launch("nerf_backward");
 }
 
-static int instance_render_impl(const float* xyzs, const int32_t* rays, const float* weights, int64_t N, int64_t M,
-                                float bound, const void* embeddings, bool fast, const inr_grid_desc* desc,
-                                const float* packed, int32_t K, float* extra_out, int32_t x_is_01, uint64_t* cursors,
-                                inr_stream_t s);
-
 int inr_instance_render(const float* xyzs, const int32_t* rays, const float* weights, int64_t N, int64_t M, float bound,
-                        const float* embeddings, const inr_grid_desc* desc, const float* packed, int32_t K,
-                        float* extra_out, int32_t x_is_01, uint64_t* cursors, inr_stream_t s) {
-  return instance_render_impl(xyzs, rays, weights, N, M, bound, embeddings, false, desc, packed, K, extra_out, x_is_01,
-                              cursors, s);
-}
-
-int inr_instance_render_fast(const float* xyzs, const int32_t* rays, const float* weights, int64_t N, int64_t M, float bound,
-                             const void* embeddings_half, const inr_grid_desc* desc, const float* packed_f16, int32_t K,
-                             float* extra_out, int32_t x_is_01, uint64_t* cursors, inr_stream_t s) {
-#if INR_MLP_FP32
-  (void)xyzs; (void)rays; (void)weights; (void)N; (void)M; (void)bound; (void)embeddings_half; (void)desc;
-  (void)packed_f16; (void)K; (void)extra_out; (void)x_is_01; (void)cursors; (void)s;
-  set_error("instance_render_fast: not available in the exact-fp32 build");
-  return INR_EINVAL;
-#else
-  return instance_render_impl(xyzs, rays, weights, N, M, bound, embeddings_half, true, desc, packed_f16, K, extra_out,
-                              x_is_01, cursors, s);
-#endif
-}
-
-int inr_instance_pack_weights_f16(const float* w0, const float* w1, const float* w2, int32_t K, float* packed) {
-  INR_REQUIRE(w0 && w1 && w2 && packed, "null pointer");
-  INR_REQUIRE(K > 0 && K <= 64 && K % 16 == 0, "K must be 16, 32, 48 or 64");
-  pack_section_f16(packed + kIns0, w0, 64, 32, 4, 8, kidx_enc);
-  pack_section_f16(packed + kIns1, w1, 64, 64, 4, 16, kidx_hidden);
-  pack_section_f16(packed + kIns2, w2, K, 64, K / 16, 16, kidx_hidden);
-  return INR_OK;
-}
-
-static int instance_render_impl(const float* xyzs, const int32_t* rays, const float* weights, int64_t N, int64_t M,
-                                float bound, const void* embeddings, bool fast, const inr_grid_desc* desc,
-                                const float* packed, int32_t K, float* extra_out, int32_t x_is_01, uint64_t* cursors,
-                                inr_stream_t s) {
+                        const void* embeddings, const inr_grid_desc* desc, const float* packed, int32_t K,
+                        float* extra_out, int32_t x_is_01, uint64_t* cursors, int32_t numerics, inr_stream_t s) {
+  const bool o = numerics == kNumericsO;
   INR_REQUIRE(N >= 0 && M >= 0 && desc, "bad argument");
   if (N == 0) return INR_OK;
   INR_REQUIRE(rays && embeddings && packed && extra_out && cursors && ((uintptr_t)cursors & 7) == 0, "null pointer");
@@ -3308,114 +3203,46 @@ static int instance_render_impl(const float* xyzs, const int32_t* rays, const fl
   INR_REQUIRE(K > 0 && K <= 64 && K % 16 == 0, "K must be 16, 32, 48 or 64");
   INR_REQUIRE(((uintptr_t)embeddings & 7) == 0 && ((uintptr_t)packed & 15) == 0 && ((uintptr_t)extra_out & 15) == 0,
               "embeddings/packed/extra_out misaligned");
-  GridDesc G;
-  int rc = make_grid_desc(desc, G);
-  if (rc) return rc;
-  const float2* e = reinterpret_cast<const float2*>(embeddings);
-  const float4* p = reinterpret_cast<const float4*>(packed);
-  const uint64_t emb_bytes64 = (uint64_t)desc->offsets[desc->num_levels] * 8ull;
-  INR_REQUIRE(emb_bytes64 < (1ull << 31), "table larger than 2 GiB is not addressable by the 32-bit gather offsets");
-  const uint32_t eb = (uint32_t)(fast ? emb_bytes64 / 2 : emb_bytes64);
+  FieldTable t;
+  if (int rc = field_table(__func__, desc, embeddings, o, t)) return rc;
+  if (int rc = check_numerics(__func__, numerics, kAcceptPlainOrO)) return rc;
   // weights + level records + two buffers of eight partial [16 rays x K] sums
   const size_t lds = (size_t)(kIns2 + K * 64) * sizeof(float) + kLevelRecBytes + 2 * (kFieldThreads / 64) * (size_t)K * 64;
   const int64_t n_groups = (N + 15) / 16;
   const int64_t as_tiles = n_groups * (kFieldThreads / 64);        // one workgroup per group
   INR_REQUIRE(n_groups < ((int64_t)1 << 31) - 65536, "too many rays for the 32-bit group cursor");
-  unsigned long long* cur = reinterpret_cast<unsigned long long*>(cursors);
-  hipStream_t st = as_stream(s);
-#define INR_IR_LAUNCH(KMT, O)                                                                                         \
-  k_instance_render<KMT, O><<<grid_for(k_instance_render<KMT, O>, lds, as_tiles), kFieldThreads, lds, st>>>(              \
-      xyzs, rays, weights, N, M, bound, e, eb, G, p, extra_out, x_is_01, cur)
-#if INR_MLP_FP32
-  (void)fast;
-  switch (K / 16) {
-    case 1: INR_IR_LAUNCH(1, false); break;
-    case 2: INR_IR_LAUNCH(2, false); break;
-    case 3: INR_IR_LAUNCH(3, false); break;
-    default: INR_IR_LAUNCH(4, false); break;
-  }
-#else
-  if (fast) {
-    switch (K / 16) {
-      case 1: INR_IR_LAUNCH(1, true); break;
-      case 2: INR_IR_LAUNCH(2, true); break;
-      case 3: INR_IR_LAUNCH(3, true); break;
-      default: INR_IR_LAUNCH(4, true); break;
-    }
-  } else {
-    switch (K / 16) {
-      case 1: INR_IR_LAUNCH(1, false); break;
-      case 2: INR_IR_LAUNCH(2, false); break;
-      case 3: INR_IR_LAUNCH(3, false); break;
-      default: INR_IR_LAUNCH(4, false); break;
-    }
-  }
-#endif
-#undef INR_IR_LAUNCH
+  with_kmt(K / 16, [&](auto kmt) {
+    with_mlp_f16(o, [&](auto fast) {
+      launch_field(k_instance_render<decltype(kmt)::value, decltype(fast)::value>, lds, as_tiles, as_stream(s), xyzs, rays,
+                   weights, N, M, bound, t.emb, t.bytes, t.G, f4(packed), extra_out, x_is_01,
+                   reinterpret_cast<unsigned long long*>(cursors));
+    });
+  });
   return check_launch("instance_render");
 }
 
-static int nerf_render_impl(const float* xyzs, const float* deltas, const int32_t* rays, const float* rays_d, int64_t N,
-                            int64_t M, float bound, const void* embeddings, bool fast, const inr_grid_desc* desc,
-                            const float* packed, float density_scale, float T_thresh, float* weights_sum, float* depth,
-                            float* image, float* weights, uint64_t* evaluated, int32_t x_is_01, inr_stream_t s);
-
 int inr_nerf_render(const float* xyzs, const float* deltas, const int32_t* rays, const float* rays_d, int64_t N,
-                    int64_t M, float bound, const float* embeddings, const inr_grid_desc* desc, const float* packed,
+                    int64_t M, float bound, const void* embeddings, const inr_grid_desc* desc, const float* packed,
                     float density_scale, float T_thresh, float* weights_sum, float* depth, float* image, float* weights,
-                    uint64_t* evaluated, int32_t x_is_01, inr_stream_t s) {
-  return nerf_render_impl(xyzs, deltas, rays, rays_d, N, M, bound, embeddings, false, desc, packed, density_scale, T_thresh,
-                          weights_sum, depth, image, weights, evaluated, x_is_01, s);
-}
-
-int inr_nerf_render_fast(const float* xyzs, const float* deltas, const int32_t* rays, const float* rays_d, int64_t N,
-                         int64_t M, float bound, const void* embeddings_half, const inr_grid_desc* desc,
-                         const float* packed_f16, float density_scale, float T_thresh, float* weights_sum, float* depth,
-                         float* image, float* weights, uint64_t* evaluated, int32_t x_is_01, inr_stream_t s) {
-#if INR_MLP_FP32
-  (void)xyzs; (void)deltas; (void)rays; (void)rays_d; (void)N; (void)M; (void)bound; (void)embeddings_half; (void)desc;
-  (void)packed_f16; (void)density_scale; (void)T_thresh; (void)weights_sum; (void)depth; (void)image; (void)weights;
-  (void)evaluated; (void)x_is_01; (void)s;
-  set_error("nerf_render_fast: not available in the exact-fp32 build");
-  return INR_EINVAL;
-#else
-  return nerf_render_impl(xyzs, deltas, rays, rays_d, N, M, bound, embeddings_half, true, desc, packed_f16, density_scale,
-                          T_thresh, weights_sum, depth, image, weights, evaluated, x_is_01, s);
-#endif
-}
-
-static int nerf_render_impl(const float* xyzs, const float* deltas, const int32_t* rays, const float* rays_d, int64_t N,
-                            int64_t M, float bound, const void* embeddings, bool fast, const inr_grid_desc* desc,
-                            const float* packed, float density_scale, float T_thresh, float* weights_sum, float* depth,
-                            float* image, float* weights, uint64_t* evaluated, int32_t x_is_01, inr_stream_t s) {
+                    uint64_t* evaluated, int32_t x_is_01, int32_t numerics, inr_stream_t s) {
+  const bool o = numerics == kNumericsO;
   INR_REQUIRE(N >= 0 && M >= 0 && desc, "bad argument");
   if (N == 0) return INR_OK;
   INR_REQUIRE(rays && rays_d && embeddings && packed && weights_sum && depth && image && evaluated, "null pointer");
   INR_REQUIRE(M == 0 || (xyzs && deltas), "null sample arrays");
   INR_REQUIRE(((uintptr_t)embeddings & 7) == 0 && ((uintptr_t)packed & 15) == 0 && ((uintptr_t)deltas & 7) == 0 &&
                   ((uintptr_t)evaluated & 7) == 0, "embeddings/packed/deltas/evaluated misaligned");
-  GridDesc G;
-  int rc = make_grid_desc(desc, G);
-  if (rc) return rc;
-  const uint64_t emb_bytes64 = (uint64_t)desc->offsets[desc->num_levels] * 8ull;
-  INR_REQUIRE(emb_bytes64 < (1ull << 31), "table larger than 2 GiB is not addressable by the 32-bit gather offsets");
+  FieldTable t;
+  if (int rc = field_table(__func__, desc, embeddings, o, t)) return rc;
+  if (int rc = check_numerics(__func__, numerics, kAcceptPlainOrO)) return rc;
   const size_t lds = kNerfFloats * sizeof(float) + kLevelRecBytes;
   const int64_t n_groups = (N + 15) / 16;
   INR_REQUIRE(n_groups < ((int64_t)1 << 31) - 65536, "too many rays for the 32-bit group cursor");
-#if !INR_MLP_FP32
-  if (fast) {
-    k_nerf_render<true><<<grid_for(k_nerf_render<true>, lds, n_groups), kFieldThreads, lds, as_stream(s)>>>(
-        xyzs, deltas, rays, rays_d, N, M, bound, reinterpret_cast<const float2*>(embeddings), (uint32_t)(emb_bytes64 / 2), G,
-        reinterpret_cast<const float4*>(packed), density_scale, T_thresh, weights_sum, depth, image, weights,
-        reinterpret_cast<unsigned long long*>(evaluated), x_is_01);
-    return check_launch("nerf_render_fast");
-  }
-#endif
-  (void)fast;
-  k_nerf_render<false><<<grid_for(k_nerf_render<false>, lds, n_groups), kFieldThreads, lds, as_stream(s)>>>(
-      xyzs, deltas, rays, rays_d, N, M, bound, reinterpret_cast<const float2*>(embeddings), (uint32_t)emb_bytes64, G,
-      reinterpret_cast<const float4*>(packed), density_scale, T_thresh, weights_sum, depth, image, weights,
-      reinterpret_cast<unsigned long long*>(evaluated), x_is_01);
+  with_mlp_f16(o, [&](auto fast) {
+    launch_field(k_nerf_render<decltype(fast)::value>, lds, n_groups, as_stream(s), xyzs, deltas, rays, rays_d, N, M, bound,
+                 t.emb, t.bytes, t.G, f4(packed), density_scale, T_thresh, weights_sum, depth, image, weights,
+                 reinterpret_cast<unsigned long long*>(evaluated), x_is_01);
+  });
   return check_launch("nerf_render");
 }
 

@@ -32,6 +32,8 @@ from ..activation import trunc_exp
 from ..encoding import get_encoder
 from .renderer import NeRFRenderer
 
+_O_NUMERICS = _lib.NUMERICS_TABLE_F16 | _lib.NUMERICS_MLP_F16      # upstream's -O: both halves (half_table + mlp_fp16)
+
 
 class _LinearFn(torch.autograd.Function):
     """y = x W^T with the weight gradient on the split-K MFMA kernel (inr_linear_wgrad): the reduction runs
@@ -538,8 +540,7 @@ class NeRFNetwork(NeRFRenderer):
         # of the hash table (512 instead of 1024 bytes of table traffic per sample); parameters, training, index
         # arithmetic, blending and the MLPs stay fp32.  Outputs differ from the fp32 table's by ~1e-3 relative.
         self.half_table = False
-        self._half_cache = None
-        self._half_cache_inst = None
+        self._half_cache = {}
         # Opt-in, the other half of `-O`: full-frame inference runs the MLP GEMMs as ONE fp16 MFMA pass (weights and
         # activations rounded to fp16, fp32 accumulation) instead of the three-pass bf16 split that keeps the default
         # fp32-class.  Outputs within a few 1e-3 of the default's; training and every other path are unaffected.
@@ -553,18 +554,21 @@ class NeRFNetwork(NeRFRenderer):
         self.last_frame_path = "fused"         # what the last large frame ran on ("fused" | "sliced" [+ " (probing)"])
 
     # ---- packed MFMA weights (cached until a weight tensor changes) ------------------------------
-    def _packed_weights(self, which):
+    def _packed_weights(self, which, numerics=0):
+        """which: "nerf" | "instance"; numerics: the value the launch that reads them is called with (INR_NUMERICS_*:
+        its MLP_F16 bit selects the fp16 packing)."""
         lib = _lib.load()
-        if which in ("nerf", "nerf_f16"):
+        mlp_f16 = numerics & _lib.NUMERICS_MLP_F16
+        if which == "nerf":
             ws = [self.sigma_net[0].weight, self.sigma_net[1].weight, self.color_net[0].weight,
                   self.color_net[1].weight, self.color_net[2].weight]
-        else:                                  # "instance", "instance_f16"
+        else:
             ws = [l.weight for l in self.instance_net]
         key = tuple((w.data_ptr(), w._version) for w in ws)
-        hit = self._packed.get(which)
+        hit = self._packed.get((which, mlp_f16))
         if hit is not None and hit[0] == key:
             return hit[1]
-        if which in ("nerf", "instance") and ws[0].is_cuda and not getattr(self, "_host_pack_only", False):
+        if not mlp_f16 and ws[0].is_cuda and not getattr(self, "_host_pack_only", False):
             # weights that live on the device are packed there (same layout and rounding as the host packers): the
             # host route costs five device->host copies, each a synchronisation - ~1 ms per occupancy update of the
             # NeRF stage, whose weights change every step
@@ -583,33 +587,37 @@ class NeRFNetwork(NeRFRenderer):
                     pb = torch.empty(lib.inr_instance_bwd_packed_floats(), dtype=f32, device=ws[0].device)
                     check(lib.inr_instance_pack_weights_device(*[ptr(w, f32, "weight") for w in dev_ws], self._k_pad,
                                                                ptr(pf), ptr(pb), stream_ptr()), "instance_pack_weights_device")
-                self._packed[which] = (key, pf)
+                self._packed[(which, mlp_f16)] = (key, pf)
                 return pf
             except RuntimeError:
                 self._host_pack_only = True          # the exact-fp32 build has no device packer
         host = [w.detach().float().cpu().contiguous() for w in ws]
-        if which.startswith("instance") and self._k_pad != self.num_instances:
+        if which == "instance" and self._k_pad != self.num_instances:
             host[2] = torch.nn.functional.pad(host[2], (0, 0, 0, self._k_pad - self.num_instances)).contiguous()
-        if which in ("nerf", "nerf_f16"):
+        if which == "nerf":
             buf = torch.empty(lib.inr_nerf_packed_floats(), dtype=torch.float32)
-            pack = lib.inr_nerf_pack_weights if which == "nerf" else lib.inr_nerf_pack_weights_f16
-            check(pack(*[host_ptr(h, torch.float32) for h in host], host_ptr(buf, torch.float32)), "nerf_pack_weights")
+            check(lib.inr_nerf_pack_weights(*[host_ptr(h, torch.float32) for h in host], host_ptr(buf, torch.float32),
+                                            mlp_f16), "nerf_pack_weights")
         else:
             buf = torch.empty(lib.inr_instance_packed_floats(self._k_pad), dtype=torch.float32)
-            pack = lib.inr_instance_pack_weights if which == "instance" else lib.inr_instance_pack_weights_f16
-            check(pack(*[host_ptr(h, torch.float32) for h in host], self._k_pad, host_ptr(buf, torch.float32)),
-                  "instance_pack_weights")
+            check(lib.inr_instance_pack_weights(*[host_ptr(h, torch.float32) for h in host], self._k_pad,
+                                                host_ptr(buf, torch.float32), mlp_f16), "instance_pack_weights")
         dev = buf.to(ws[0].device)
-        self._packed[which] = (key, dev)
+        self._packed[(which, mlp_f16)] = (key, dev)
         return dev
 
-    def _half_table(self):
-        """fp16 copy of the NeRF table (the opt-in -O paths), refreshed whenever the fp32 master changes."""
-        emb = self.encoder.embeddings
+    def _table_ptr(self, encoder, numerics=0):
+        """Device pointer of the table a fused launch called with ``numerics`` gathers from: the encoder's fp32
+        parameter, or under INR_NUMERICS_TABLE_F16 (the opt-in -O paths) an fp16 copy of it, refreshed whenever the fp32
+        master changes."""
+        emb = encoder.embeddings
+        if not numerics & _lib.NUMERICS_TABLE_F16:
+            return ptr(emb.data, torch.float32, "embeddings")
         key = (emb.data_ptr(), emb._version)
-        if self._half_cache is None or self._half_cache[0] != key:
-            self._half_cache = (key, emb.detach().to(torch.float16).contiguous())
-        return self._half_cache[1]
+        hit = self._half_cache.get(id(encoder))
+        if hit is None or hit[0] != key:
+            hit = self._half_cache[id(encoder)] = (key, emb.detach().to(torch.float16).contiguous())
+        return ptr(hit[1], torch.float16, "embeddings")
 
     def _needs_grad(self, params):
         return torch.is_grad_enabled() and any(p.requires_grad for p in params)
@@ -632,19 +640,16 @@ class NeRFNetwork(NeRFRenderer):
         geo = torch.empty(M, self.geo_feat_dim, dtype=torch.float32, device=dev) if want_geo else None
         if want_rgb:
             d = d.contiguous().float()
+        numerics = 0
         if (want_rgb and not want_geo and self.half_table and self.mlp_fp16
                 and (not self.training or not self.encoder.embeddings.requires_grad)):
             # opt-in -O numerics for a NeRF that is only evaluated: inference, and the FROZEN NeRF of the instance stage
             # (its forward is bound by every XCD pulling the whole table through its fabric port: half the bytes)
-            check(lib.inr_nerf_forward_fast(ptr(x, torch.float32, "x"), ptr(d, torch.float32, "d"), M, None, float(self.bound),
-                                            ptr(self._half_table(), torch.float16), self.encoder.desc,
-                                            ptr(self._packed_weights("nerf_f16")), 1.0, ptr(sigma), ptr(rgb), stream_ptr()),
-                  "nerf_forward_fast")
-            return sigma, rgb, geo
+            numerics = _O_NUMERICS
         check(lib.inr_nerf_forward(ptr(x, torch.float32, "x"), ptr(d, torch.float32, "d", allow_none=not want_rgb),
-                                   M, None, float(self.bound), ptr(self.encoder.embeddings.data, torch.float32),
-                                   self.encoder.desc, ptr(self._packed_weights("nerf")), 1.0, ptr(sigma),
-                                   ptr(rgb, allow_none=True), ptr(geo, allow_none=True), stream_ptr()),
+                                   M, None, float(self.bound), self._table_ptr(self.encoder, numerics),
+                                   self.encoder.desc, ptr(self._packed_weights("nerf", numerics)), 1.0, ptr(sigma),
+                                   ptr(rgb, allow_none=True), ptr(geo, allow_none=True), numerics, stream_ptr()),
               "nerf_forward")
         return sigma, rgb, geo
 
@@ -759,30 +764,13 @@ class NeRFNetwork(NeRFRenderer):
             shq = self.sh_table(rays_d)
         sigma = torch.empty(M, dtype=torch.float32, device=dev)
         rgb = torch.empty(M, 3, dtype=torch.float32, device=dev)
-        half = self.half_table and not self.training
-        if half:
-            # opt-in (upstream's -O / fp16 storage): the eval kernel gathers from a half-precision copy of the table,
-            # refreshed whenever the fp32 master changes
-            self._half_table()
-        if self.mlp_fp16 and not self.training:
-            # opt-in (the other half of upstream's -O): one fp16 MFMA pass per MLP GEMM instead of the fp32-class split
-            table = self._half_cache[1] if half else self.encoder.embeddings.data
-            check(lib.inr_nerf_forward_table_fast(ptr(x01, torch.float32, "x01", allow_none=M == 0),
-                                                  ptr(ray_ids, torch.int32, "ray_ids", allow_none=M == 0), ptr(shq), M,
-                                                  float(self.bound), ptr(table), 1 if half else 0,
-                                                  self.encoder.desc, ptr(self._packed_weights("nerf_f16")), 1.0,
-                                                  ptr(sigma, allow_none=M == 0), ptr(rgb, allow_none=M == 0), stream_ptr()),
-                  "nerf_forward_table_fast")
-            return sigma, rgb
-        if half:
-            check(lib.inr_nerf_forward_table_half(ptr(x01, torch.float32, "x01", allow_none=M == 0),
-                                                  ptr(ray_ids, torch.int32, "ray_ids", allow_none=M == 0), ptr(shq), M,
-                                                  float(self.bound), ptr(self._half_cache[1], torch.float16),
-                                                  self.encoder.desc, ptr(self._packed_weights("nerf")), 1.0,
-                                                  ptr(sigma, allow_none=M == 0), ptr(rgb, allow_none=M == 0), stream_ptr()),
-                  "nerf_forward_table_half")
-            return sigma, rgb
-        if self._use_slices(M):
+        numerics = 0
+        if not self.training:
+            # opt-in, the two halves of upstream's -O: the eval kernel gathers from a half-precision copy of the table
+            # (fp16 storage), and runs one fp16 MFMA pass per MLP GEMM instead of the fp32-class split
+            numerics = ((_lib.NUMERICS_TABLE_F16 if self.half_table else 0)
+                        | (_lib.NUMERICS_MLP_F16 if self.mlp_fp16 else 0))
+        if not numerics and self._use_slices(M):
             # sliced frame path (round 5): the three finest levels by a level-major pre-pass (every XCD's L2 then holds
             # the one level the chip is working on), the fused kernel on the other thirteen; same numbers bit for bit
             need = lib.inr_nerf_forward_table_sliced_workspace_bytes(M) // 4
@@ -803,10 +791,10 @@ class NeRFNetwork(NeRFRenderer):
         self._open_slice_probe()
         check(lib.inr_nerf_forward_table(ptr(x01, torch.float32, "x01", allow_none=M == 0),
                                          ptr(ray_ids, torch.int32, "ray_ids", allow_none=M == 0), ptr(shq), M,
-                                         float(self.bound), ptr(self.encoder.embeddings.data, torch.float32),
-                                         self.encoder.desc, ptr(self._packed_weights("nerf")), 1.0,
-                                         ptr(sigma, allow_none=M == 0), ptr(rgb, allow_none=M == 0), stream_ptr()),
-              "nerf_forward_table")
+                                         float(self.bound), self._table_ptr(self.encoder, numerics),
+                                         self.encoder.desc, ptr(self._packed_weights("nerf", numerics)), 1.0,
+                                         ptr(sigma, allow_none=M == 0), ptr(rgb, allow_none=M == 0), numerics,
+                                         stream_ptr()), "nerf_forward_table")
         self._close_slice_probe()
         return sigma, rgb
 
@@ -1001,14 +989,14 @@ class NeRFNetwork(NeRFRenderer):
         image = torch.empty(N, 3, dtype=torch.float32, device=dev)
         wbuf = torch.empty(max(M, 1), dtype=torch.float32, device=dev) if want_weights else None
         evaluated = torch.zeros(33, dtype=torch.int64, device=dev)     # [0] evaluated samples, [1..32] the launch's group cursors
-        fn, table, packed = lib.inr_nerf_render, self.encoder.embeddings.data, "nerf"
-        if self.half_table and self.mlp_fp16 and not self.training:        # opt-in: upstream's -O numerics
-            fn, table, packed = lib.inr_nerf_render_fast, self._half_table(), "nerf_f16"
-        check(fn(ptr(xyzs, torch.float32, "xyzs", allow_none=M == 0), ptr(deltas, torch.float32, "deltas", allow_none=M == 0),
-                 ptr(rays, torch.int32, "rays"), ptr(rays_d.contiguous(), torch.float32, "rays_d"), N, M, float(self.bound),
-                 ptr(table), self.encoder.desc, ptr(self._packed_weights(packed)), float(self.density_scale),
-                 float(T_thresh), ptr(ws), ptr(depth), ptr(image), ptr(wbuf, allow_none=True), ptr(evaluated),
-                 1 if normalised else 0, stream_ptr()), "nerf_render")
+        numerics = _O_NUMERICS if self.half_table and self.mlp_fp16 and not self.training else 0     # opt-in
+        check(lib.inr_nerf_render(ptr(xyzs, torch.float32, "xyzs", allow_none=M == 0),
+                                  ptr(deltas, torch.float32, "deltas", allow_none=M == 0), ptr(rays, torch.int32, "rays"),
+                                  ptr(rays_d.contiguous(), torch.float32, "rays_d"), N, M, float(self.bound),
+                                  self._table_ptr(self.encoder, numerics), self.encoder.desc,
+                                  ptr(self._packed_weights("nerf", numerics)), float(self.density_scale), float(T_thresh),
+                                  ptr(ws), ptr(depth), ptr(image), ptr(wbuf, allow_none=True), ptr(evaluated),
+                                  1 if normalised else 0, numerics, stream_ptr()), "nerf_render")
         return ws, depth, image, wbuf, evaluated[:1]
 
     @torch.no_grad()
@@ -1022,24 +1010,13 @@ class NeRFNetwork(NeRFRenderer):
         N, M = rays.shape[0], xyzs.shape[0]
         out = torch.empty(N, self._k_pad, dtype=torch.float32, device=rays.device)
         cursors = torch.zeros(32, dtype=torch.int64, device=rays.device)        # the launch's dynamic group schedule
-        if self.half_table and self.mlp_fp16 and not self.training:
-            # opt-in, upstream's -O numerics for the instance field too: fp16 copy of its table, one-pass fp16 MLP
-            emb = self.instance_encoder.embeddings
-            key = (emb.data_ptr(), emb._version)
-            if self._half_cache_inst is None or self._half_cache_inst[0] != key:
-                self._half_cache_inst = (key, emb.detach().to(torch.float16).contiguous())
-            check(lib.inr_instance_render_fast(ptr(xyzs, torch.float32, "xyzs", allow_none=M == 0), ptr(rays, torch.int32, "rays"),
-                                               ptr(weights, torch.float32, "weights", allow_none=M == 0), N, M,
-                                               float(self.bound), ptr(self._half_cache_inst[1], torch.float16),
-                                               self.instance_encoder.desc, ptr(self._packed_weights("instance_f16")),
-                                               self._k_pad, ptr(out), 1 if normalised else 0, ptr(cursors), stream_ptr()),
-                  "instance_render_fast")
-            return out if self._k_pad == self.num_instances else out[:, :self.num_instances].contiguous()
+        # opt-in, upstream's -O numerics for the instance field too: fp16 copy of its table, one-pass fp16 MLP
+        numerics = _O_NUMERICS if self.half_table and self.mlp_fp16 and not self.training else 0
         check(lib.inr_instance_render(ptr(xyzs, torch.float32, "xyzs", allow_none=M == 0), ptr(rays, torch.int32, "rays"),
                                       ptr(weights, torch.float32, "weights", allow_none=M == 0), N, M, float(self.bound),
-                                      ptr(self.instance_encoder.embeddings.data, torch.float32),
-                                      self.instance_encoder.desc, ptr(self._packed_weights("instance")),
-                                      self._k_pad, ptr(out), 1 if normalised else 0, ptr(cursors), stream_ptr()),
+                                      self._table_ptr(self.instance_encoder, numerics), self.instance_encoder.desc,
+                                      ptr(self._packed_weights("instance", numerics)), self._k_pad, ptr(out),
+                                      1 if normalised else 0, ptr(cursors), numerics, stream_ptr()),
               "instance_render")
         return out if self._k_pad == self.num_instances else out[:, :self.num_instances].contiguous()
 

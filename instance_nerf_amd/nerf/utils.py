@@ -813,8 +813,8 @@ class Trainer:
         # the EMA: no autocast, no GradScaler (nothing trained is ever stored or accumulated in half precision, so there
         # is nothing to scale).  What -O switches on are -O's numerics for every field that is only EVALUATED: the
         # evaluation / test renders, and at train time the FROZEN NeRF of the instance stage (NeRFNetwork.half_table +
-        # NeRFNetwork.mlp_fp16 -> inr_nerf_forward_fast: the fp16 copy of its table halves the bytes every XCD pulls
-        # through its fabric port for a random-ray batch, the MLP runs as one fp16 MFMA pass; instance step 0.872 ->
+        # NeRFNetwork.mlp_fp16 -> inr_nerf_forward with the -O numerics: the fp16 copy of its table halves the bytes every
+        # XCD pulls through its fabric port for a random-ray batch, the MLP runs as one fp16 MFMA pass; instance step 0.872 ->
         # 0.848 ms, loss within 1 % of the fp32 step over 50 steps:
         # tests/test_gpu_parity.py::test_train_time_O_keeps_the_instance_stage_within_one_percent)
         self.mute, self.fp16 = mute, bool(fp16)

@@ -204,13 +204,13 @@ def nerf_forward(x: Tensor, d: Tensor, embeddings: Tensor, sigma_w0: Tensor, sig
     M = x.shape[0]
     host = [w.detach().float().cpu().contiguous() for w in (sigma_w0, sigma_w1, color_w0, color_w1, color_w2)]
     buf = torch.empty(lib.inr_nerf_packed_floats(), dtype=F32)
-    check(lib.inr_nerf_pack_weights(*[_lib.host_ptr(h, F32) for h in host], _lib.host_ptr(buf, F32)), "nerf_pack_weights")
+    check(lib.inr_nerf_pack_weights(*[_lib.host_ptr(h, F32) for h in host], _lib.host_ptr(buf, F32), 0), "nerf_pack_weights")
     packed = buf.to(x.device)
     sigma, rgb = torch.empty(M, dtype=F32, device=x.device), torch.empty(M, 3, dtype=F32, device=x.device)
     if M:
         check(lib.inr_nerf_forward(ptr(x), ptr(d), M, None, float(bound), ptr(embeddings, F32, "embeddings"),
                                    _desc(offsets, scales, resolutions, hashed), ptr(packed), 1.0, ptr(sigma), ptr(rgb), None,
-                                   stream_ptr()), "nerf_forward")
+                                   0, stream_ptr()), "nerf_forward")
     return sigma, rgb
 
 

@@ -86,6 +86,11 @@ out["inr_instance_pack_weights:K_65"] = call("inr_instance_pack_weights", args_f
 out["inr_instance_pack_weights_device:K_80"] = call("inr_instance_pack_weights_device", args_for("inr_instance_pack_weights_device", a3=80))
 out["inr_instance_head_backward:K_80"] = call("inr_instance_head_backward", args_for("inr_instance_head_backward", a4=80))
 out["inr_instance_render:K_80"] = call("inr_instance_render", args_for("inr_instance_render", a7=ctypes.byref(ok_desc), a9=80))
+# a numerics value the entry point does not take (TABLE_F16 alone: instance_render takes 0 or both bits)
+out["inr_nerf_forward_table:numerics_4"] = call("inr_nerf_forward_table", args_for(
+    "inr_nerf_forward_table", a6=ctypes.byref(ok_desc), a11=4))
+out["inr_instance_render:numerics_1"] = call("inr_instance_render", args_for(
+    "inr_instance_render", a7=ctypes.byref(ok_desc), a13=_lib.NUMERICS_TABLE_F16))
 out["inr_cross_entropy:K_65"] = call("inr_cross_entropy", args_for("inr_cross_entropy", a3=65))
 out["inr_composite_rays_extra_forward:K_65"] = call("inr_composite_rays_extra_forward", args_for("inr_composite_rays_extra_forward", a5=65))
 out["inr_instance_packed_floats:K_65"] = [int(lib.inr_instance_packed_floats(65)), (lib.inr_last_error() or b"").decode()]

@@ -76,8 +76,8 @@ def test_no_cpu_fallback():
         raymarching.near_far_from_aabb(torch.zeros(4, 3), torch.ones(4, 3), torch.tensor([-1., -1, -1, 1, 1, 1]))
 
 
-def test_host_side_packing_roundtrip():
-    """Weight packing is host code.  Default build: bf16 head + remainder per weight
+def test_host_side_packing_roundtrip_default_numerics():
+    """Weight packing is host code.  Default build, numerics 0: bf16 head + remainder per weight
     ([mt][step][hi|lo][lane][8]); every weight appears exactly once and hi + lo reproduces it to 2^-16."""
     import ctypes
     import numpy as np
@@ -86,7 +86,7 @@ def test_host_side_packing_roundtrip():
     rng = np.random.default_rng(0)
     ws = [rng.normal(size=s).astype(np.float32) for s in [(64, 32), (16, 64), (64, 31), (64, 64), (3, 64)]]
     out = np.zeros(lib.inr_nerf_packed_floats(), np.float32)
-    rc = lib.inr_nerf_pack_weights(*[w.ctypes.data_as(ctypes.c_void_p) for w in ws], out.ctypes.data_as(ctypes.c_void_p))
+    rc = lib.inr_nerf_pack_weights(*[w.ctypes.data_as(ctypes.c_void_p) for w in ws], out.ctypes.data_as(ctypes.c_void_p), 0)
     assert rc == 0
     h = out.view(np.uint16).astype(np.uint32)
     vals = (h << 16).view(np.float32).reshape(-1, 2, 64, 8)          # [mt*step, hi|lo, lane, e]

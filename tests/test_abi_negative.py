@@ -58,21 +58,18 @@ def test_null_pointers_are_rejected_with_einval_and_a_message(results):
         assert rc == EINVAL and msg, (name, rc, msg)
 
 
-def test_negative_sizes_are_rejected_before_any_launch(results):
-    """Valid (host) pointers, every size -1: INR_EINVAL - except the entry points that take no size at all, whose launch
-    then fails on this GPU-less box with INR_ELAUNCH / INR_ENODEV (still a return code, still alive), and the host-side
-    packers, which succeed on valid host buffers."""
+def test_negative_sizes_and_numerics_are_rejected_before_any_launch(results):
+    """Valid (host) pointers, every size -1 (and every `numerics` -1, the host-side packers included): INR_EINVAL -
+    except the entry points that take no size at all, whose launch then fails on this GPU-less box with INR_ELAUNCH /
+    INR_ENODEV (still a return code, still alive)."""
     from instance_nerf_amd import _lib
     import ctypes
-    no_sizes_host = {"inr_nerf_pack_weights", "inr_nerf_pack_weights_f16"}
     for name, (restype, argtypes) in _lib._SIGS.items():
         if name in SIZE_QUERIES or name in NO_BAD_VALUE or name in ("inr_abi_version", "inr_last_error"):
             continue
         rc, msg = results[f"{name}:negative"]
         has_int = any(t in (ctypes.c_int32, ctypes.c_int64) for t in argtypes)
-        if name in no_sizes_host:
-            assert rc == 0, (name, rc, msg)
-        elif not has_int:
+        if not has_int:
             assert rc in (EINVAL, ELAUNCH, ENODEV) and msg, (name, rc, msg)
         elif name == "inr_set_march_mode":
             assert rc == 0                              # -1 IS a mode (automatic)
@@ -108,6 +105,7 @@ def test_size_queries_never_report_a_size_for_bad_arguments(results):
     ("inr_set_march_mode:mode_7", "mode"), ("inr_roi_align_3d_set_mode:mode_9", "mode"),
     ("inr_roi_align_3d_forward:zero_bins", "size"), ("inr_roi_align_3d_backward_ws:workspace_too_small", "workspace"),
     ("inr_nerf_forward_table_sliced:12_levels", "16-level"),
+    ("inr_nerf_forward_table:numerics_4", "numerics"), ("inr_instance_render:numerics_1", "numerics"),
 ])
 def test_named_limits_of_the_header(results, key, needle):
     rc, msg = results[key]

@@ -571,8 +571,8 @@ def test_instance_render_with_O_numerics(level_table, room, room_bitfield):
 
 def test_frozen_nerf_of_the_instance_stage_takes_O_numerics_when_asked(level_table, room, room_bitfield):
     """half_table + mlp_fp16 also cover a NeRF that is only EVALUATED during training - the frozen NeRF of the instance
-    stage (inr_nerf_forward_fast) - and nothing that is trained: instance-stage renders move by a little (and the
-    instance gradients with them), NeRF-stage training renders and gradients keep their bits."""
+    stage (inr_nerf_forward with the -O numerics) - and nothing that is trained: instance-stage renders move by a little (and
+    the instance gradients with them), NeRF-stage training renders and gradients keep their bits."""
     from oracle import field
     p = field.init_params(seed=47, table=level_table, table_std=1.0, K=16)
     ro, rd = scene_rays(room, 600, cam=2, seed=61)
@@ -3064,8 +3064,8 @@ def test_shade_ahead_is_bit_identical_to_the_inline_head(room):
 def test_train_time_O_keeps_the_instance_stage_within_one_percent(room):
     """Trainer(fp16=True, stage="instance") - upstream's -O for the stage this repository trains with a frozen NeRF: the
     frozen field's forward runs with -O's numerics (fp16 copy of its table: half the bytes every XCD pulls through its
-    fabric port; single-pass fp16 MLP: inr_nerf_forward_fast) while everything that is TRAINED - instance table, instance
-    MLP, their gradients, Adam's moments - stays fp32 (no GradScaler: nothing trained is ever stored in half precision).
+    fabric port; single-pass fp16 MLP: inr_nerf_forward with the -O numerics) while everything that is TRAINED - instance
+    table, instance MLP, their gradients, Adam's moments - stays fp32 (no GradScaler: nothing trained is ever stored in half precision).
     50 steps from the same parameters on the same batches: the loss stays within 1 % of the fp32 run at every step."""
     from instance_nerf_amd.nerf import NeRFNetwork
     from instance_nerf_amd.nerf.provider import SyntheticRoomDataset

@@ -26,7 +26,7 @@ for view in (0, 3):
         dbg = torch.zeros(4096, dtype=torch.int64, device=dev)
         check(lib.inr_nerf_forward(ptr(xyzs), ptr(dirs), M, None, 1.0, ptr(net.encoder.embeddings.data), net.encoder.desc,
                                    ptr(net._packed_weights("nerf")), 1.0, ptr(sigma), ptr(rgb), ptr(dbg.view(torch.float32)),
-                                   _lib.stream_ptr()), "fwd")
+                                   0, _lib.stream_ptr()), "fwd")
         torch.cuda.synchronize()
     t = dbg.cpu().numpy().reshape(-1, 2)
     t = t[t[:, 1] > 0]
