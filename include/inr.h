@@ -38,8 +38,9 @@ extern "C" {
  * without a bump: a stale library or an external caller built against the old header was only rejected by accident).
  * instance_nerf_amd/_lib.py refuses a library whose version differs from the one it was written against.
  * 10: inr_instance_lattice, inr_instance_volume_stats.
- * 11: the fp16 variants folded into their base entry points as a `numerics` argument (INR_NUMERICS_*). */
-#define INR_ABI_VERSION 11
+ * 11: the fp16 variants folded into their base entry points as a `numerics` argument (INR_NUMERICS_*).
+ * 12: inr_mesh_workspace_bytes, inr_mesh_count, inr_mesh_emit. */
+#define INR_ABI_VERSION 12
 #define INR_MAX_LEVELS 16
 
 enum {
@@ -539,6 +540,61 @@ int inr_instance_lattice(const float* ax_w, const float* ax_l, const float* ax_h
 int inr_instance_volume_stats(const uint8_t* labels, const float* confidence, int32_t W, int32_t L, int32_t H, int32_t K,
                               void* workspace, int64_t workspace_bytes, int32_t* counts, int32_t* boxes, float* conf_sum,
                               inr_stream_t s);
+
+/* ---- iso-surface meshes of a lattice field (no counterpart in the reference tree: upstream's Trainer.save_mesh runs
+ * marching cubes on the host).  MARCHING TETRAHEDRA over the Kuhn split of every lattice cell: translation-invariant, so
+ * neighbouring cells agree on every face diagonal and the surface is closed and edge-manifold for any field.
+ *
+ * Field: `field` float [W, L, H] read with an element stride (`field_stride` = 4 reads channel 3 of an rgbsigma
+ * [W, L, H, 4] volume in place when `field` points at that channel).  A lattice point is INSIDE when field >= iso (NaN:
+ * outside) and, with select >= 0, labels == select (labels uint8 [W, L, H], nullable when select = -1; select -1..254).
+ * For interpolation a value is clamped to [iso - clamp, iso + clamp]; NaN and masked-out points take iso - clamp.
+ * clamp > 0 and finite, iso - clamp < iso in fp32.
+ *
+ * cap = 1 surrounds the lattice with one layer of virtual outside points (value iso - clamp), so a surface that reaches
+ * the border is closed; the extended lattice is [W+2, L+2, H+2] and a virtual point's coordinate continues the first /
+ * last step of its axis (ax[0] - (ax[1] - ax[0]), ax[n-1] + (ax[n-1] - ax[n-2]); for an axis of length 1: ax[0] -/+ the
+ * `ext_*` argument of that axis).  cap = 0 visits the (W-1)(L-1)(H-1) real cells only.
+ *
+ * Tables.  Cube corner code c = 4 dw + 2 dl + dh.  A cell is split into six tetrahedra, one per order in which the axes
+ * are added on the way from corner 0 to corner 7; tetrahedron t has the corners (tetrahedron vertices 0..3)
+ *   t0 wlh: 0 4 6 7   t1 whl: 0 4 5 7   t2 lwh: 0 2 6 7   t3 lhw: 0 2 3 7   t4 hwl: 0 1 5 7   t5 hlw: 0 1 3 7
+ * Every tetrahedron edge runs from a lattice point p to p + d, d = (dw, dl, dh) != 0; p OWNS the edge, and the 7
+ * directions are ordered by their code 4 dw + 2 dl + dh = 1..7: (0,0,1) (0,1,0) (0,1,1) (1,0,0) (1,0,1) (1,1,0) (1,1,1).
+ * Tetrahedron edges by their two tetrahedron vertices: e0 = 01, e1 = 02, e2 = 03, e3 = 12, e4 = 13, e5 = 23.  Case m =
+ * sum of 2^i over the inside tetrahedron vertices i; triangles as edge triples:
+ *    1: e0 e1 e2            2: e0 e4 e3            3: e1 e2 e4, e1 e4 e3   4: e1 e3 e5            5: e0 e5 e2, e0 e3 e5
+ *    6: e0 e4 e5, e0 e5 e1  7: e2 e4 e5            8: e2 e5 e4            9: e0 e1 e5, e0 e5 e4  10: e0 e5 e3, e0 e2 e5
+ *   11: e1 e5 e3           12: e1 e3 e4, e1 e4 e2 13: e0 e3 e4           14: e0 e2 e1            0, 15: none
+ * The triples are wound for t0, t3, t4 (even axis permutations); t1, t2, t5 are mirror images and swap the second and
+ * third vertex of every triangle.  Normals then point from inside to outside: a closed surface has positive volume.
+ *
+ * A crossed edge p -> q = p + d (exactly one end inside) gets ONE vertex, in fp32 and in this order of operations (the
+ * library is built without contraction and with IEEE division): a, b = clamped values at p, q; t = (iso - a) / (b - a);
+ * x = xp + t * (xq - xp) per axis; colour (rgb float [W, L, H, 4], channels 0..2, nullable together with `colors`)
+ * cp + t * (cq - cp), a virtual end taking the real end's colour.
+ *
+ * Canonical order, decided by scans (no atomics: two calls give identical bits).  Points and cells are walked in
+ * (w, l, h) order of the (extended) lattice, h fastest.  Vertices: by owner point, then by direction code.  Triangles: by
+ * cell (named by its corner 0), then tetrahedron 0..5, then the table's order.  face_labels (uint8 [F], nullable, needs
+ * `labels`): the label of the tetrahedron's inside vertex with the largest clamped value, the lowest tetrahedron vertex on
+ * ties (it may be 255 where the label volume and the field disagree about occupancy).
+ *
+ * inr_mesh_workspace_bytes: size of the caller-owned workspace (4-byte aligned); INR_EINVAL for sizes < 1, cap not 0 / 1,
+ * or a lattice whose 12 * (extended) points do not fit an int32.  inr_mesh_count: three launches on `s` (classify, scan,
+ * vertex offsets); fills the workspace and writes counts int32 [2] = (V, F) on the device.  inr_mesh_emit: with the SAME
+ * field arguments and the workspace inr_mesh_count filled (read-only here), V and F as read back by the caller (rows
+ * beyond them are never written): vertices float [V, 3], faces int32 [F, 3], colors float [V, 3], face_labels; two
+ * launches on `s`, none when V = F = 0.  All buffers 4-byte aligned.                                                  */
+int64_t inr_mesh_workspace_bytes(int32_t W, int32_t L, int32_t H, int32_t cap);
+int inr_mesh_count(const float* field, int32_t field_stride, float iso, float clamp, const uint8_t* labels /*nullable*/,
+                   int32_t select, int32_t W, int32_t L, int32_t H, int32_t cap, void* workspace, int64_t workspace_bytes,
+                   int32_t* counts, inr_stream_t s);
+int inr_mesh_emit(const float* field, int32_t field_stride, float iso, float clamp, const uint8_t* labels /*nullable*/,
+                  int32_t select, const float* rgb /*nullable*/, const float* ax_w, const float* ax_l, const float* ax_h,
+                  int32_t W, int32_t L, int32_t H, float ext_w, float ext_l, float ext_h, int32_t cap,
+                  const void* workspace, int64_t workspace_bytes, int32_t V, int32_t F, float* vertices, int32_t* faces,
+                  float* colors /*nullable*/, uint8_t* face_labels /*nullable*/, inr_stream_t s);
 
 /* ---- 3-D RoIAlign ("next" row f2; replaces roi_align.roi_align.roi_align_3d, the one FFI call in the
  * reference tree: /root/reference/nerf_rcnn/model/utils.py:604-609).  torchvision roi_align semantics

@@ -117,6 +117,10 @@ _SIGS = {
     "inr_instance_lattice": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_float, P, POINTER(GridDesc), P, c_float,
                                        c_float, P, POINTER(GridDesc), P, c_int32, P, P, P, P]),
     "inr_instance_volume_stats": (c_int32, [P, P, c_int32, c_int32, c_int32, c_int32, P, c_int64, P, P, P, P]),
+    "inr_mesh_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "inr_mesh_count": (c_int32, [P, c_int32, c_float, c_float, P, c_int32, c_int32, c_int32, c_int32, c_int32, P, c_int64, P, P]),
+    "inr_mesh_emit": (c_int32, [P, c_int32, c_float, c_float, P, c_int32, P, P, P, P, c_int32, c_int32, c_int32, c_float,
+                                c_float, c_float, c_int32, P, c_int64, c_int32, c_int32, P, P, P, P, P]),
     "inr_roi_align_3d_set_mode": (c_int32, [c_int32]),
     "inr_roi_align_3d_forward": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32,
                                            c_int32, c_int32, c_float, P, P]),
@@ -138,7 +142,7 @@ _SIGS = {
 }
 EXPORTS = tuple(_SIGS)
 
-ABI_VERSION = 11         # include/inr.h INR_ABI_VERSION this binding was written against
+ABI_VERSION = 12         # include/inr.h INR_ABI_VERSION this binding was written against
 INSTANCE_STATS_WORKSPACE_BYTES = 512 * 64 * 8 * 4      # include/inr.h INR_INSTANCE_STATS_WORKSPACE_BYTES
 _lib = None
 

@@ -249,3 +249,171 @@ def extract_instances(model, bbox_min=None, bbox_max=None, max_side=160, res=Non
     counts, boxes, csum = volume_stats(labels, conf, K)
     scores = torch.where(counts > 0, csum / counts.clamp_min(1).float(), torch.zeros_like(csum))
     return {"labels": labels, "confidence": conf, "res": res, "counts": counts, "boxes": boxes, "scores": scores}
+
+
+# ---- triangle meshes of the density field ---------------------------------------------------------------------------
+# Half-width of the band of density logits the vertex interpolation sees, around iso = log(threshold / density_scale).
+# 2.0 keeps sigma within a factor e^2 (~7.4) of the threshold on either side - the range over which a trained density
+# actually rises across a surface.  Outside that band the logit says nothing about where the surface is: empty space sits
+# at the extraction's floor (log 1e-30 = -69) and solid space saturates, so an unclamped interpolation between -69 and +5
+# would put every vertex within 4 % of a cell from its inside corner (the staircase of the voxel grid), and a much
+# smaller value would snap every vertex to the middle of its edge.
+MESH_CLAMP = 2.0
+
+
+def mesh_from_lattice(field, iso, axes, ext, labels=None, select=-1, rgb=None, face_labels=False, cap=True,
+                      clamp=MESH_CLAMP):
+    """Marching tetrahedra on the GPU (``inr_mesh_count`` + ``inr_mesh_emit``, semantics in include/inr.h) of a lattice
+    field that is already on the device.  ``field`` float32 [W, L, H], dense or a channel view of a dense [W, L, H, C]
+    tensor (read in place); ``axes`` = the three coordinate axes; ``ext`` = three floats, the step of the virtual layer
+    for an axis of length 1; ``labels`` uint8 [W, L, H] with ``select`` = -1 or a channel; ``rgb`` float32 [W, L, H, 4]
+    (channels 0..2 colour the vertices).  One host read-back of (V, F) between the two calls.
+    -> dict vertices float32 [V, 3], faces int32 [F, 3], colors float32 [V, 3] / None, face_labels uint8 [F] / None."""
+    from . import _lib
+    lib = _lib.load()
+    if not field.is_cuda:
+        raise RuntimeError("mesh_from_lattice: field must be a GPU tensor (the HIP path has no CPU fallback)")
+    if field.dim() != 3 or field.dtype != torch.float32:
+        raise RuntimeError("mesh_from_lattice: field must be float32 [W, L, H]")
+    W, L, H = (int(v) for v in field.shape)
+    if W * L * H == 0:
+        raise RuntimeError("mesh_from_lattice: empty lattice")
+    stride = int(field.stride(2))
+    if stride < 1 or tuple(field.stride()) != (L * H * stride, H * stride, stride):      # not a channel view of a dense volume
+        field, stride = field.contiguous(), 1
+    dev = field.device
+    if labels is not None:
+        _lib.ptr(labels, torch.uint8, "labels")
+        if tuple(labels.shape) != (W, L, H):
+            raise RuntimeError("mesh_from_lattice: labels must be [W, L, H]")
+    if rgb is not None and (tuple(rgb.shape) != (W, L, H, 4) or rgb.dtype != torch.float32 or not rgb.is_contiguous()):
+        raise RuntimeError("mesh_from_lattice: rgb must be contiguous float32 [W, L, H, 4]")
+    if face_labels and labels is None:
+        raise RuntimeError("mesh_from_lattice: face_labels needs labels")
+    ax = [a.contiguous().float() for a in axes]
+    if [int(a.shape[0]) for a in ax] != [W, L, H]:
+        raise RuntimeError("mesh_from_lattice: the axes do not match the field")
+    cap = 1 if cap else 0
+    nbytes = int(lib.inr_mesh_workspace_bytes(W, L, H, cap))
+    _lib.check(min(nbytes, 0), "mesh_workspace_bytes")
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    P = _lib.ptr
+    fptr, lptr = _lib.c_void_p(field.data_ptr()), P(labels, torch.uint8, "labels", allow_none=True)
+    head = (fptr, stride, float(iso), float(clamp), lptr, int(select))
+    _lib.check(lib.inr_mesh_count(*head, W, L, H, cap, P(ws), nbytes, P(counts), _lib.stream_ptr()), "mesh_count")
+    V, F = (int(v) for v in counts.tolist())                 # the one host read-back
+    vertices = torch.empty(V, 3, dtype=torch.float32, device=dev)
+    faces = torch.empty(F, 3, dtype=torch.int32, device=dev)
+    colors = torch.empty(V, 3, dtype=torch.float32, device=dev) if rgb is not None else None
+    flab = torch.empty(F, dtype=torch.uint8, device=dev) if face_labels else None
+    if V or F:
+        _lib.check(lib.inr_mesh_emit(*head, P(rgb, allow_none=True), P(ax[0]), P(ax[1]), P(ax[2]), W, L, H, float(ext[0]),
+                                     float(ext[1]), float(ext[2]), cap, P(ws), nbytes, V, F, P(vertices, allow_none=V == 0),
+                                     P(faces, allow_none=F == 0), P(colors, allow_none=True), P(flab, allow_none=True),
+                                     _lib.stream_ptr()), "mesh_emit")
+    return {"vertices": vertices, "faces": faces, "colors": colors, "face_labels": flab}
+
+
+def _mesh_lattices_composable(model, bbox_min, bbox_max, res, thresh, need_labels, need_rgb, chunk=1 << 20):
+    """The lattices of ``mesh_lattices`` through ``density()`` / ``color()`` / ``instance()`` over chunks of points."""
+    dev = next(model.parameters()).device
+    b = float(model.bound)
+    W, L, H = (int(v) for v in res)
+    pts = lattice(bbox_min, bbox_max, res, dev)
+    logit = torch.empty(pts.shape[0], dtype=torch.float32, device=dev)
+    rgbs = torch.zeros(W, L, H, 4, dtype=torch.float32, device=dev) if need_rgb else None
+    dirs = torch.from_numpy(VIEW_DIRS).to(dev)
+    for s in range(0, pts.shape[0], chunk):
+        x = pts[s:s + chunk].clamp(-b, b).contiguous()
+        den = model.density(x)
+        logit[s:s + chunk] = torch.log(den["sigma"].clamp_min(1e-30))
+        if need_rgb:
+            acc = torch.zeros(x.shape[0], 3, dtype=torch.float32, device=dev)
+            for v in range(dirs.shape[0]):
+                acc += model.color(x, dirs[v].expand(x.shape[0], 3).contiguous(), geo_feat=den["geo_feat"])
+            rgbs.view(-1, 4)[s:s + chunk, :3] = acc / dirs.shape[0]
+    labels = _instances_composable(model, bbox_min, bbox_max, res, thresh, chunk)[0] if need_labels else None
+    return logit.view(W, L, H), labels, rgbs
+
+
+@torch.no_grad()
+def mesh_lattices(model, bbox_min=None, bbox_max=None, resolution=256, res=None, threshold=10.0, labels=False, colors=True,
+                  fused=True):
+    """The field launches of ``extract_mesh``, once: -> dict ``field`` (density logit float32 [W, L, H], possibly a view),
+    ``labels`` (uint8 [W, L, H] or None), ``rgb`` (float32 [W, L, H, 4] or None), ``axes``, ``ext``, ``iso``, ``res``,
+    ``bbox_min``, ``bbox_max``.  ``mesh_of_lattices`` turns it into any number of meshes."""
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError("extract_mesh: the model must be on a GPU (the HIP path has no CPU fallback)")
+    if not float(threshold) > 0:
+        raise ValueError("extract_mesh: threshold must be > 0 (the surface is density_scale * sigma = threshold)")
+    if labels and not getattr(model, "num_instances", 0):
+        raise ValueError("extract_mesh: the model has no instance head (num_instances = 0)")
+    b = float(model.bound)
+    bbox_min = np.asarray([-b, -b, -b] if bbox_min is None else bbox_min, dtype=np.float32)
+    bbox_max = np.asarray([b, b, b] if bbox_max is None else bbox_max, dtype=np.float32)
+    res = grid_resolution(bbox_min, bbox_max, resolution) if res is None else np.asarray(res, dtype=np.int64)
+    iso = float(np.log(np.float32(threshold) / np.float32(getattr(model, "density_scale", 1.0)), dtype=np.float32))
+    axes = _cached_axes(bbox_min, bbox_max, res, dev)
+    was_training = model.training
+    model.eval()
+    try:
+        field = lab = rgb = None
+        if fused and labels and hasattr(model, "instance_lattice"):
+            out = model.instance_lattice(axes, float(threshold), want_logit=True)
+            if out is not None:
+                lab, _, field = out
+        if fused and (colors or not labels) and hasattr(model, "forward_lattice") and (field is not None or not labels):
+            cached = getattr(model, "_view_dirs_dev", None)
+            if cached is None or cached[0].device != dev:
+                d = torch.from_numpy(VIEW_DIRS).to(dev)
+                cached = model._view_dirs_dev = (d, model.encoder_dir(d).contiguous() if hasattr(model, "encoder_dir") else None)
+            rgb = model.forward_lattice(axes, cached[0], logit_min=float(np.log(1e-30)), sh=cached[1])
+            if rgb is not None and field is None:
+                field = rgb[..., 3]
+        if field is None or (colors and rgb is None):
+            field, lab, rgb = _mesh_lattices_composable(model, bbox_min, bbox_max, res, float(threshold), labels, colors)
+    finally:
+        model.train(was_training)
+    ext = [float(np.float32(bbox_max[a]) - np.float32(bbox_min[a])) for a in range(3)]
+    return {"field": field, "labels": lab, "rgb": rgb if colors else None, "axes": axes, "ext": ext, "iso": iso, "res": res,
+            "bbox_min": bbox_min, "bbox_max": bbox_max}
+
+
+def mesh_of_lattices(lat, instance=None, face_labels=None, colors=True, cap=True, clamp=MESH_CLAMP):
+    """One mesh of the lattices ``mesh_lattices`` returned (two mesh launches and one read-back; no field launch)."""
+    if instance is not None and (lat["labels"] is None or not 0 <= int(instance) < LABEL_EMPTY):
+        raise ValueError("extract_mesh: instance needs a model with an instance head and a channel 0..254")
+    want_fl = (lat["labels"] is not None and instance is None) if face_labels is None else bool(face_labels)
+    out = mesh_from_lattice(lat["field"], lat["iso"], lat["axes"], lat["ext"], labels=lat["labels"],
+                            select=-1 if instance is None else int(instance), rgb=lat["rgb"] if colors else None,
+                            face_labels=want_fl, cap=cap, clamp=clamp)
+    out["res"] = lat["res"]
+    return out
+
+
+@torch.no_grad()
+def extract_mesh(model, bbox_min=None, bbox_max=None, resolution=256, res=None, threshold=10.0, instance=None,
+                 face_labels=None, colors=True, cap=True, clamp=MESH_CLAMP, fused=True):
+    """Triangle mesh of the surface ``density_scale * sigma = threshold`` (the sigma the renderer composites, as in
+    ``extract_instances``) on the voxel-centre lattice of ``extract_rgbsigma`` (longest side ``resolution``, default box
+    [-bound, bound]^3), extracted on the GPU by marching tetrahedra (include/inr.h, "iso-surface meshes").  -> dict on the
+    model's device: ``vertices`` float32 [V, 3], ``faces`` int32 [F, 3] (normals point out of the dense side),
+    ``colors`` float32 [V, 3] or None (rgb averaged over the four extraction view directions), ``face_labels`` uint8 [F]
+    or None, ``res``.  Nothing above the threshold gives empty tensors, not an error.
+
+    The scalar field is the density LOGIT, log sigma, and ``iso = log(threshold / density_scale)`` is formed once on the
+    host in fp32; vertices are interpolated in the logit, clamped to ``iso +- clamp``.  Upstream interpolates sigma
+    itself: sigma jumps by orders of magnitude across one cell at a surface, which pins every vertex to its inside corner;
+    the logit is close to linear there.
+
+    ``instance=k``: the surface of the voxels whose instance label (``extract_instances``' arg-max) is k, closed on its
+    own.  ``face_labels`` (default: on for a model with an instance head, when ``instance`` is None): per face, the
+    label of the tetrahedron's densest inside corner; 255 where the label volume and the logit disagree at the
+    threshold's rounding.  ``cap``: close surfaces that reach the box.  Labels come from ``instance_lattice`` (one fused
+    launch, with the logit), colours from ``forward_lattice``; ``fused=False`` and shapes the fused kernels do not cover
+    go through ``density()`` / ``color()`` / ``instance()``.  The mesh kernels themselves have no fallback."""
+    need_labels = instance is not None or (bool(getattr(model, "num_instances", 0)) if face_labels is None else bool(face_labels))
+    lat = mesh_lattices(model, bbox_min, bbox_max, resolution, res, threshold, labels=need_labels, colors=colors, fused=fused)
+    return mesh_of_lattices(lat, instance=instance, face_labels=face_labels, colors=colors, cap=cap, clamp=clamp)

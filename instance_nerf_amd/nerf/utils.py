@@ -1543,6 +1543,53 @@ class Trainer:
             self.model.train(was_training)
         return write_instance_masks_npz(path, result, **write_kw)
 
+    def _mesh_path(self, save_path):
+        return save_path or os.path.join(self.workspace or ".", "meshes", f"{self.name}_{self.epoch}.ply")
+
+    def save_mesh(self, save_path=None, resolution=256, threshold=10):
+        """Upstream's call: the surface ``density_scale * sigma = threshold`` of the trained field as a binary PLY at
+        ``save_path`` (default ``<workspace>/meshes/<name>_<epoch>.ply``), extracted on the GPU (``extract.extract_mesh``:
+        marching tetrahedra instead of upstream's host-side marching cubes), with vertex colours and - for a model with an
+        instance head - a ``label`` per face.  Eval mode for the extraction, the previous mode restored.  -> path."""
+        from ..extract import extract_mesh
+        from ..mesh_io import write_ply
+        path = self._mesh_path(save_path)
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            m = extract_mesh(self.model, resolution=resolution, threshold=threshold)
+        finally:
+            self.model.train(was_training)
+        self.log(f"==> saving mesh to {path} ({m['vertices'].shape[0]} vertices, {m['faces'].shape[0]} faces)")
+        return write_ply(path, m["vertices"], m["faces"], m["colors"], m["face_labels"])
+
+    def save_instance_meshes(self, save_path=None, resolution=256, threshold=10, min_faces=1):
+        """The labelled scene mesh at ``save_path`` (as ``save_mesh``) and one closed mesh per instance channel k >= 1
+        with at least ``min_faces`` faces at ``<save_path minus .ply>_instance_<k>.ply`` (k = the channel, as
+        ``masks.write_instance_masks_npz`` numbers them).  The field is evaluated once; only the mesh launches repeat
+        per instance.  -> {"scene": path, "instances": {k: path}}."""
+        from ..extract import mesh_lattices, mesh_of_lattices
+        from ..mesh_io import write_ply
+        path = self._mesh_path(save_path)
+        stem = path[:-4] if path.lower().endswith(".ply") else path
+        was_training = self.model.training
+        self.model.eval()
+        try:
+            lat = mesh_lattices(self.model, resolution=resolution, threshold=threshold, labels=True, colors=True)
+            scene = mesh_of_lattices(lat)
+            written = {"scene": write_ply(path, scene["vertices"], scene["faces"], scene["colors"], scene["face_labels"]),
+                       "instances": {}}
+            present = torch.bincount(lat["labels"].reshape(-1).long(), minlength=256).tolist()
+            for k in range(1, int(self.model.num_instances)):
+                if not present[k]:
+                    continue
+                m = mesh_of_lattices(lat, instance=k)
+                if m["faces"].shape[0] >= max(int(min_faces), 1):
+                    written["instances"][k] = write_ply(f"{stem}_instance_{k}.ply", m["vertices"], m["faces"], m["colors"])
+        finally:
+            self.model.train(was_training)
+        return written
+
     # -- checkpoint (upstream keys: epoch, global_step, stats, model, optimizer, lr_scheduler, ema, mean_count, mean_density)
     def save_checkpoint(self, name=None, full=False, best=False, remove_old=True, path=None):
         """``full``: with optimizer / scheduler / EMA state (to resume training); ``best``: written to
