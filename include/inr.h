@@ -39,8 +39,9 @@ extern "C" {
  * instance_nerf_amd/_lib.py refuses a library whose version differs from the one it was written against.
  * 10: inr_instance_lattice, inr_instance_volume_stats.
  * 11: the fp16 variants folded into their base entry points as a `numerics` argument (INR_NUMERICS_*).
- * 12: inr_mesh_workspace_bytes, inr_mesh_count, inr_mesh_emit. */
-#define INR_ABI_VERSION 12
+ * 12: inr_mesh_workspace_bytes, inr_mesh_count, inr_mesh_emit.
+ * 13: inr_components_workspace_bytes, inr_components_label, inr_components_filter. */
+#define INR_ABI_VERSION 13
 #define INR_MAX_LEVELS 16
 
 enum {
@@ -595,6 +596,46 @@ int inr_mesh_emit(const float* field, int32_t field_stride, float iso, float cla
                   int32_t W, int32_t L, int32_t H, float ext_w, float ext_l, float ext_h, int32_t cap,
                   const void* workspace, int64_t workspace_bytes, int32_t V, int32_t F, float* vertices, int32_t* faces,
                   float* colors /*nullable*/, uint8_t* face_labels /*nullable*/, inr_stream_t s);
+
+/* ---- connected components of a label volume (no counterpart in the reference tree; drops floaters from the masks and
+ * meshes above).  Input: `labels` uint8 [W, L, H], h fastest, 255 = empty, as inr_instance_lattice writes it.  The
+ * linear index of voxel (iw, il, ih) is (iw * L + il) * H + ih; W * L * H must be below 2^31.
+ *
+ * Two voxels are CONNECTED when they are neighbours and carry the same label != 255; a component is a class of the
+ * transitive closure.  Neighbours: connectivity = 6, the face neighbours (exactly one of |dw|, |dl|, |dh| is 1, the
+ * others 0); connectivity = 26, every (dw, dl, dh) in {-1, 0, 1}^3 except (0, 0, 0).  Any other value: INR_EINVAL.  The
+ * volume does not wrap around.  A component is named by its ROOT: the smallest linear index among its voxels.
+ *   roots int32 [W, L, H]: the root of the voxel's component, -1 for an empty voxel (4-byte aligned).
+ * The definition does not depend on a traversal order, and the output is bit-identical between calls although the
+ * kernels use integer atomics (min on parents, add on sizes: both order-independent).
+ *
+ * Keep rule (inr_components_filter), for every channel c in first_channel..K-1 (K = 1..255, first_channel = 0..K): the
+ * SIZE of a component is its number of voxels; a component of label c SURVIVES when size >= min_voxels (>= 1) and, with
+ * keep_largest = 1, it is also the largest component of label c - among components of equal size the one with the
+ * lowest root (so at most one survives per channel).  keep_largest is 0 or 1.
+ *   labels_out uint8 [W, L, H]: the label where the voxel's component survives, 255 where it does not.  Labels below
+ *     first_channel or >= K (255 included) are copied through unchanged.  May alias `labels`.
+ *   confidence_out float [W, L, H] (nullable; needs `confidence`; may alias it): confidence where the output label
+ *     equals the input label, 0 where the voxel was dropped.
+ *   n_components int32 [K]: components of label c before the rule; kept_voxels int32 [K]: voxels of label c in
+ *     surviving components; kept_root int32 [K]: with keep_largest = 1 the root of the survivor, -1 when none;
+ *     always -1 with keep_largest = 0.  Channels below first_channel report 0, 0, -1.
+ * Feed labels_out to inr_instance_volume_stats for counts, boxes and confidence sums of what was kept.
+ *
+ * inr_components_workspace_bytes: size of the caller-owned workspace (8-byte aligned); INR_EINVAL for sizes < 1 or
+ * W * L * H >= 2^31.  inr_components_label additionally needs ceil(W / 8) * ceil(L / 8) * ceil(H / 64) <= 2^23 tiles (one
+ * workgroup each; only a volume far thinner than a tile in two axes, such as 1 x 1 x 2^30, comes near) and returns
+ * INR_EINVAL beyond.  inr_components_label: three launches on `s` - one workgroup per 8 x 8 x 64 tile labels it in LDS,
+ * one pass unites across tile faces, one pass compresses every voxel to its root and counts component sizes into the
+ * workspace.  inr_components_filter: with the SAME labels, the roots and the workspace inr_components_label filled
+ * (sizes are read, the per-channel scratch behind them is written); four launches on `s`.                           */
+int64_t inr_components_workspace_bytes(int32_t W, int32_t L, int32_t H);
+int inr_components_label(const uint8_t* labels, int32_t W, int32_t L, int32_t H, int32_t connectivity, void* workspace,
+                         int64_t workspace_bytes, int32_t* roots, inr_stream_t s);
+int inr_components_filter(const uint8_t* labels, const int32_t* roots, const float* confidence /*nullable*/, int32_t W,
+                          int32_t L, int32_t H, int32_t K, int32_t first_channel, int32_t min_voxels, int32_t keep_largest,
+                          void* workspace, int64_t workspace_bytes, uint8_t* labels_out, float* confidence_out /*nullable*/,
+                          int32_t* n_components, int32_t* kept_voxels, int32_t* kept_root, inr_stream_t s);
 
 /* ---- 3-D RoIAlign ("next" row f2; replaces roi_align.roi_align.roi_align_3d, the one FFI call in the
  * reference tree: /root/reference/nerf_rcnn/model/utils.py:604-609).  torchvision roi_align semantics

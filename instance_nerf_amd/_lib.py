@@ -121,6 +121,10 @@ _SIGS = {
     "inr_mesh_count": (c_int32, [P, c_int32, c_float, c_float, P, c_int32, c_int32, c_int32, c_int32, c_int32, P, c_int64, P, P]),
     "inr_mesh_emit": (c_int32, [P, c_int32, c_float, c_float, P, c_int32, P, P, P, P, c_int32, c_int32, c_int32, c_float,
                                 c_float, c_float, c_int32, P, c_int64, c_int32, c_int32, P, P, P, P, P]),
+    "inr_components_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32]),
+    "inr_components_label": (c_int32, [P, c_int32, c_int32, c_int32, c_int32, P, c_int64, P, P]),
+    "inr_components_filter": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, P, c_int64,
+                                        P, P, P, P, P, P]),
     "inr_roi_align_3d_set_mode": (c_int32, [c_int32]),
     "inr_roi_align_3d_forward": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32,
                                            c_int32, c_int32, c_float, P, P]),
@@ -142,7 +146,7 @@ _SIGS = {
 }
 EXPORTS = tuple(_SIGS)
 
-ABI_VERSION = 12         # include/inr.h INR_ABI_VERSION this binding was written against
+ABI_VERSION = 13         # include/inr.h INR_ABI_VERSION this binding was written against
 INSTANCE_STATS_WORKSPACE_BYTES = 512 * 64 * 8 * 4      # include/inr.h INR_INSTANCE_STATS_WORKSPACE_BYTES
 _lib = None
 

@@ -184,6 +184,173 @@ def volume_stats(labels, confidence, K):
             torch.from_numpy(csum).to(dev))
 
 
+# ---- connected components of a label volume (include/inr.h, "connected components") --------------------------------------
+def _neighbour_offsets(connectivity):
+    if connectivity not in (6, 26):
+        raise ValueError("connectivity must be 6 or 26")
+    offs = [(dw, dl, dh) for dw in (-1, 0, 1) for dl in (-1, 0, 1) for dh in (-1, 0, 1) if (dw, dl, dh) != (0, 0, 0)]
+    return [o for o in offs if connectivity == 26 or abs(o[0]) + abs(o[1]) + abs(o[2]) == 1]
+
+
+def _check_label_volume(labels, who):
+    if not torch.is_tensor(labels) or labels.dim() != 3 or labels.dtype != torch.uint8:
+        raise ValueError(f"{who}: labels must be a uint8 [W, L, H] tensor")
+    if labels.numel() == 0 or labels.numel() >= 2 ** 31:
+        raise ValueError(f"{who}: the volume must hold 1 .. 2^31 - 1 voxels")
+
+
+def _side(n, d):
+    """The slices of an axis of length n that pair every voxel (first) with its neighbour at offset d (second)."""
+    return (slice(max(0, -d), n - max(0, d)), slice(max(0, d), n - max(0, -d)))
+
+
+def _label_composable(labels, connectivity):
+    """Roots by neighbour-min propagation with pointer jumping, in plain torch on the volume's device: every voxel takes
+    the smallest parent among its connected neighbours, hands it to its own parent (a scatter-min), and all parent chains
+    are then halved until they are flat; repeated until nothing changes.  Parents only decrease and stay inside the
+    component, so the fixed point is the smallest linear index of the component."""
+    W, L, H = (int(v) for v in labels.shape)
+    N = W * L * H
+    lab = labels.contiguous()
+    live = (lab != LABEL_EMPTY).reshape(-1)
+    idx = torch.arange(N, dtype=torch.int64, device=lab.device)
+    pairs = []
+    for dw, dl, dh in _neighbour_offsets(connectivity):
+        (aw, bw), (al, bl), (ah, bh) = _side(W, dw), _side(L, dl), _side(H, dh)
+        a, b = (aw, al, ah), (bw, bl, bh)
+        if lab[a].numel():
+            pairs.append((a, b, (lab[a] == lab[b]) & (lab[a] != LABEL_EMPTY)))
+    parent = idx.clone()
+    while True:
+        low = parent.clone().view(W, L, H)
+        pv = parent.view(W, L, H)
+        for a, b, same in pairs:
+            low[a] = torch.where(same, torch.minimum(low[a], pv[b]), low[a])
+        low = low.reshape(-1)
+        nxt = torch.minimum(parent, low)
+        nxt.scatter_reduce_(0, parent, low, "amin")
+        while True:
+            hop = nxt[nxt]
+            if torch.equal(hop, nxt):
+                break
+            nxt = hop
+        if torch.equal(nxt, parent):
+            break
+        parent = nxt
+    return torch.where(live, parent, torch.full_like(parent, -1)).to(torch.int32).view(W, L, H)
+
+
+def _components_workspace(lib, W, L, H, dev):
+    from . import _lib
+    nbytes = int(lib.inr_components_workspace_bytes(W, L, H))
+    _lib.check(min(nbytes, 0), "components_workspace_bytes")
+    return torch.empty(nbytes // 8, dtype=torch.int64, device=dev), nbytes
+
+
+def _label_hip(labels, connectivity):
+    from . import _lib
+    lib = _lib.load()
+    W, L, H = (int(v) for v in labels.shape)
+    labels = labels.contiguous()
+    ws, nbytes = _components_workspace(lib, W, L, H, labels.device)
+    roots = torch.empty(W, L, H, dtype=torch.int32, device=labels.device)
+    _lib.check(lib.inr_components_label(_lib.ptr(labels, torch.uint8, "labels"), W, L, H, int(connectivity), _lib.ptr(ws),
+                                        nbytes, _lib.ptr(roots), _lib.stream_ptr()), "components_label")
+    return labels, roots, ws, nbytes
+
+
+def label_components(labels, connectivity=6, fused=True):
+    """Connected components of a label volume (uint8 [W, L, H], ``LABEL_EMPTY`` = empty): two voxels are connected when
+    they are neighbours (``connectivity`` 6 = faces, 26 = faces, edges and corners) and carry the same label.
+    -> ``roots`` int32 [W, L, H]: the smallest linear index ``(iw * L + il) * H + ih`` of the voxel's component, -1 for an
+    empty voxel.  A GPU tensor goes through ``inr_components_label`` (three HIP launches; identical bits on every call);
+    a CPU tensor, or ``fused=False``, through the same semantics in plain torch."""
+    _check_label_volume(labels, "label_components")
+    _neighbour_offsets(connectivity)
+    if labels.is_cuda and fused:
+        return _label_hip(labels, connectivity)[1]
+    return _label_composable(labels, int(connectivity))
+
+
+def _filter_composable(labels, roots, confidence, K, first, min_voxels, largest):
+    W, L, H = (int(v) for v in labels.shape)
+    N = W * L * H
+    dev = labels.device
+    lab = labels.reshape(-1).long()
+    r = roots.reshape(-1).long()
+    sizes = torch.bincount(r[r >= 0], minlength=N)
+    is_root = r == torch.arange(N, dtype=torch.int64, device=dev)
+    root_idx = torch.nonzero(is_root & (lab >= first) & (lab < K)).reshape(-1)
+    ch, sz = lab[root_idx], sizes[root_idx]
+    n_components = torch.bincount(ch, minlength=K)[:K]
+    ok = sz >= min_voxels
+    kept_root = torch.full((K,), -1, dtype=torch.int64, device=dev)
+    if largest:
+        key = torch.where(ok, sz * (1 << 31) + ((1 << 31) - 1 - root_idx), torch.zeros_like(sz))     # size, then lowest root
+        best = torch.zeros(K, dtype=torch.int64, device=dev)
+        best.scatter_reduce_(0, ch, key, "amax")
+        kept_root = torch.where(best > 0, (1 << 31) - 1 - best % (1 << 31), kept_root)
+        ok = ok & (root_idx == kept_root[ch])
+    kept_voxels = torch.zeros(K, dtype=torch.int64, device=dev)
+    kept_voxels.scatter_add_(0, ch[ok], sz[ok])
+    survives = torch.zeros(N, dtype=torch.bool, device=dev)
+    survives[root_idx[ok]] = True
+    filtered = (lab >= first) & (lab < K)
+    keep = ~filtered | survives[r.clamp_min(0)]
+    out = torch.where(keep, labels.reshape(-1), torch.full_like(labels.reshape(-1), LABEL_EMPTY)).view(W, L, H)
+    conf = None
+    if confidence is not None:
+        conf = torch.where(keep, confidence.reshape(-1), torch.zeros_like(confidence.reshape(-1))).view(W, L, H)
+    return out, conf, n_components.to(torch.int32), kept_voxels.to(torch.int32), kept_root.to(torch.int32)
+
+
+def filter_components(labels, confidence=None, K=None, connectivity=6, keep="largest", min_voxels=1, skip_background=True,
+                      fused=True):
+    """Labels the components of ``labels`` (``label_components``) and applies the keep rule to every channel
+    ``first..K-1`` (``first`` = 1 with ``skip_background``, else 0): a component survives when it has at least
+    ``min_voxels`` voxels and, with ``keep="largest"``, is the channel's largest (the lowest root among equals);
+    ``keep="all"`` applies the size rule alone.  Labels below ``first`` or >= K pass through.  -> dict: ``labels`` uint8
+    (``LABEL_EMPTY`` where a voxel was dropped), ``confidence`` (0 there; None without the input), ``roots`` int32 (of the
+    INPUT volume), ``n_components`` / ``kept_voxels`` / ``kept_root`` int32 [K] (``kept_root`` -1 when nothing survives and
+    always with ``keep="all"``).  GPU tensors: ``inr_components_label`` + ``inr_components_filter``; CPU tensors or
+    ``fused=False``: plain torch, same semantics."""
+    _check_label_volume(labels, "filter_components")
+    _neighbour_offsets(connectivity)
+    if K is None or not 1 <= int(K) <= LABEL_EMPTY:
+        raise ValueError(f"filter_components: K must be 1..{LABEL_EMPTY}")
+    if keep not in ("largest", "all"):
+        raise ValueError('filter_components: keep must be "largest" or "all"')
+    if int(min_voxels) < 1:
+        raise ValueError("filter_components: min_voxels must be >= 1")
+    K, min_voxels, largest = int(K), int(min_voxels), keep == "largest"
+    first = min(1, K) if skip_background else 0
+    if confidence is not None and (tuple(confidence.shape) != tuple(labels.shape) or confidence.dtype != torch.float32 or
+                                   confidence.device != labels.device):
+        raise ValueError("filter_components: confidence must be float32, of the labels' shape and device")
+    if labels.is_cuda and fused:
+        from . import _lib
+        lib = _lib.load()
+        W, L, H = (int(v) for v in labels.shape)
+        labels, roots, ws, nbytes = _label_hip(labels, connectivity)
+        dev = labels.device
+        out = torch.empty_like(labels)
+        conf = confidence.contiguous() if confidence is not None else None
+        conf_out = torch.empty_like(conf) if conf is not None else None
+        per = torch.empty(3, K, dtype=torch.int32, device=dev)
+        P = _lib.ptr
+        _lib.check(lib.inr_components_filter(P(labels), P(roots), P(conf, torch.float32, "confidence", allow_none=True), W, L, H,
+                                             K, first, min_voxels, int(largest), P(ws), nbytes, P(out),
+                                             P(conf_out, allow_none=True), P(per[0]), P(per[1]), P(per[2]),
+                                             _lib.stream_ptr()), "components_filter")
+        n_components, kept_voxels, kept_root = per[0], per[1], per[2]
+    else:
+        roots = _label_composable(labels, int(connectivity))
+        out, conf_out, n_components, kept_voxels, kept_root = _filter_composable(labels, roots, confidence, K, first,
+                                                                                 min_voxels, largest)
+    return {"labels": out, "confidence": conf_out, "roots": roots, "n_components": n_components, "kept_voxels": kept_voxels,
+            "kept_root": kept_root}
+
+
 def _instances_composable(model, bbox_min, bbox_max, res, sigma_thresh, chunk):
     """The composable form of the fused launch, with its semantics: voxel centres clamped to [-bound, bound], occupied
     when density_scale * sigma >= sigma_thresh, arg-max over the K real channels (torch.argmax: lowest on ties), max-softmax
@@ -209,7 +376,7 @@ def _instances_composable(model, bbox_min, bbox_max, res, sigma_thresh, chunk):
 
 @torch.no_grad()
 def extract_instances(model, bbox_min=None, bbox_max=None, max_side=160, res=None, sigma_thresh=None, fused=True,
-                      chunk=1 << 20):
+                      chunk=1 << 20, components=None, connectivity=6, min_component_voxels=1):
     """The trained instance field as a 3-D segmentation on the lattice of ``extract_rgbsigma`` (voxel centres, longest
     side ``max_side``, default box [-bound, bound]^3).  A voxel is occupied when ``density_scale * sigma`` (the sigma the
     renderer composites) is >= ``sigma_thresh`` (default ``model.density_thresh``).  -> dict:
@@ -223,7 +390,14 @@ def extract_instances(model, bbox_min=None, bbox_max=None, max_side=160, res=Non
 
     Tensors stay on the model's device.  The fused path is one HIP launch for the labels (``NeRFNetwork.instance_lattice``)
     and one for the statistics; two calls give identical bits.  ``fused=False`` (and shapes the fused kernels do not
-    cover) runs the composable path - ``density()`` + ``instance()`` over chunks of points - with the same semantics."""
+    cover) runs the composable path - ``density()`` + ``instance()`` over chunks of points - with the same semantics.
+
+    ``components="largest"`` / ``"all"`` (default None: off) drops floaters first: the label volume goes through
+    ``filter_components`` (``connectivity``, ``min_component_voxels``; channel 0, the walls, is left alone), so ``labels``,
+    ``confidence``, ``counts``, ``boxes`` and ``scores`` describe the kept voxels, and the result gains ``n_components``
+    int32 [K] (components per channel before the rule) and ``raw_counts`` int64 [K] (voxels per channel before it)."""
+    if components not in (None, "largest", "all"):
+        raise ValueError('extract_instances: components must be None, "largest" or "all"')
     if not getattr(model, "num_instances", 0):
         raise ValueError("extract_instances: the model has no instance head (num_instances = 0)")
     dev = next(model.parameters()).device
@@ -246,9 +420,15 @@ def extract_instances(model, bbox_min=None, bbox_max=None, max_side=160, res=Non
     finally:
         model.train(was_training)
     labels, conf = out
+    extra = {}
+    if components is not None:
+        extra["raw_counts"] = torch.bincount(labels.reshape(-1).long(), minlength=LABEL_EMPTY + 1)[:K]
+        kept = filter_components(labels, conf, K=K, connectivity=connectivity, keep=components,
+                                 min_voxels=min_component_voxels, skip_background=True, fused=fused)
+        labels, conf, extra["n_components"] = kept["labels"], kept["confidence"], kept["n_components"]
     counts, boxes, csum = volume_stats(labels, conf, K)
     scores = torch.where(counts > 0, csum / counts.clamp_min(1).float(), torch.zeros_like(csum))
-    return {"labels": labels, "confidence": conf, "res": res, "counts": counts, "boxes": boxes, "scores": scores}
+    return {"labels": labels, "confidence": conf, "res": res, "counts": counts, "boxes": boxes, "scores": scores, **extra}
 
 
 # ---- triangle meshes of the density field ---------------------------------------------------------------------------
@@ -339,10 +519,16 @@ def _mesh_lattices_composable(model, bbox_min, bbox_max, res, thresh, need_label
 
 @torch.no_grad()
 def mesh_lattices(model, bbox_min=None, bbox_max=None, resolution=256, res=None, threshold=10.0, labels=False, colors=True,
-                  fused=True):
+                  fused=True, components=None, connectivity=6, min_component_voxels=1):
     """The field launches of ``extract_mesh``, once: -> dict ``field`` (density logit float32 [W, L, H], possibly a view),
     ``labels`` (uint8 [W, L, H] or None), ``rgb`` (float32 [W, L, H, 4] or None), ``axes``, ``ext``, ``iso``, ``res``,
-    ``bbox_min``, ``bbox_max``.  ``mesh_of_lattices`` turns it into any number of meshes."""
+    ``bbox_min``, ``bbox_max``.  ``mesh_of_lattices`` turns it into any number of meshes.  ``components="largest"`` /
+    ``"all"`` filters the label volume once (``filter_components``, channel 0 left alone), so ``instance=k`` then meshes
+    the kept component(s) of k only."""
+    if components not in (None, "largest", "all"):
+        raise ValueError('mesh_lattices: components must be None, "largest" or "all"')
+    if components is not None and not labels:
+        raise ValueError("mesh_lattices: components filters the label volume and needs labels=True")
     dev = next(model.parameters()).device
     if dev.type != "cuda":
         raise RuntimeError("extract_mesh: the model must be on a GPU (the HIP path has no CPU fallback)")
@@ -376,6 +562,9 @@ def mesh_lattices(model, bbox_min=None, bbox_max=None, resolution=256, res=None,
             field, lab, rgb = _mesh_lattices_composable(model, bbox_min, bbox_max, res, float(threshold), labels, colors)
     finally:
         model.train(was_training)
+    if components is not None and lab is not None:
+        lab = filter_components(lab, None, K=int(model.num_instances), connectivity=connectivity, keep=components,
+                                min_voxels=min_component_voxels, skip_background=True, fused=fused)["labels"]
     ext = [float(np.float32(bbox_max[a]) - np.float32(bbox_min[a])) for a in range(3)]
     return {"field": field, "labels": lab, "rgb": rgb if colors else None, "axes": axes, "ext": ext, "iso": iso, "res": res,
             "bbox_min": bbox_min, "bbox_max": bbox_max}
@@ -395,7 +584,8 @@ def mesh_of_lattices(lat, instance=None, face_labels=None, colors=True, cap=True
 
 @torch.no_grad()
 def extract_mesh(model, bbox_min=None, bbox_max=None, resolution=256, res=None, threshold=10.0, instance=None,
-                 face_labels=None, colors=True, cap=True, clamp=MESH_CLAMP, fused=True):
+                 face_labels=None, colors=True, cap=True, clamp=MESH_CLAMP, fused=True, min_component_voxels=0,
+                 connectivity=6):
     """Triangle mesh of the surface ``density_scale * sigma = threshold`` (the sigma the renderer composites, as in
     ``extract_instances``) on the voxel-centre lattice of ``extract_rgbsigma`` (longest side ``resolution``, default box
     [-bound, bound]^3), extracted on the GPU by marching tetrahedra (include/inr.h, "iso-surface meshes").  -> dict on the
@@ -413,7 +603,22 @@ def extract_mesh(model, bbox_min=None, bbox_max=None, resolution=256, res=None, 
     label of the tetrahedron's densest inside corner; 255 where the label volume and the logit disagree at the
     threshold's rounding.  ``cap``: close surfaces that reach the box.  Labels come from ``instance_lattice`` (one fused
     launch, with the logit), colours from ``forward_lattice``; ``fused=False`` and shapes the fused kernels do not cover
-    go through ``density()`` / ``color()`` / ``instance()``.  The mesh kernels themselves have no fallback."""
+    go through ``density()`` / ``color()`` / ``instance()``.  The mesh kernels themselves have no fallback.
+
+    ``min_component_voxels`` > 0 (scene mesh only, default 0 = off) drops floaters: the lattice points with
+    ``field >= iso`` form a one-channel label volume (0 inside, 255 outside), components (``connectivity``) below that
+    size are dropped (``filter_components``), and the kept points are meshed with ``select=0``.  No face labels then."""
+    if int(min_component_voxels) > 0:
+        if instance is not None or face_labels:
+            raise ValueError("extract_mesh: min_component_voxels filters the scene mesh (no instance, no face_labels)")
+        lat = mesh_lattices(model, bbox_min, bbox_max, resolution, res, threshold, labels=False, colors=colors, fused=fused)
+        inside = lat["field"] >= lat["iso"]
+        solid = torch.where(inside, torch.zeros_like(inside, dtype=torch.uint8),
+                            torch.full_like(inside, LABEL_EMPTY, dtype=torch.uint8)).contiguous()
+        lat["labels"] = filter_components(solid, None, K=1, connectivity=connectivity, keep="all",
+                                          min_voxels=int(min_component_voxels), skip_background=False,
+                                          fused=fused)["labels"]
+        return mesh_of_lattices(lat, instance=0, face_labels=False, colors=colors, cap=cap, clamp=clamp)
     need_labels = instance is not None or (bool(getattr(model, "num_instances", 0)) if face_labels is None else bool(face_labels))
     lat = mesh_lattices(model, bbox_min, bbox_max, resolution, res, threshold, labels=need_labels, colors=colors, fused=fused)
     return mesh_of_lattices(lat, instance=instance, face_labels=face_labels, colors=colors, cap=cap, clamp=clamp)

@@ -1546,18 +1546,29 @@ class Trainer:
     def _mesh_path(self, save_path):
         return save_path or os.path.join(self.workspace or ".", "meshes", f"{self.name}_{self.epoch}.ply")
 
+    # Floater removal of the mesh writers (extract.filter_components).  Attributes, not arguments: the two calls keep
+    # upstream's signature.  mesh_components None / "largest" / "all" and mesh_connectivity 6 / 26 apply to
+    # save_instance_meshes, mesh_min_component_voxels (0 = off) to save_mesh.
+    mesh_components = None
+    mesh_connectivity = 6
+    mesh_min_component_voxels = 0
+
     def save_mesh(self, save_path=None, resolution=256, threshold=10):
         """Upstream's call: the surface ``density_scale * sigma = threshold`` of the trained field as a binary PLY at
         ``save_path`` (default ``<workspace>/meshes/<name>_<epoch>.ply``), extracted on the GPU (``extract.extract_mesh``:
         marching tetrahedra instead of upstream's host-side marching cubes), with vertex colours and - for a model with an
-        instance head - a ``label`` per face.  Eval mode for the extraction, the previous mode restored.  -> path."""
+        instance head - a ``label`` per face.  Eval mode for the extraction, the previous mode restored.  -> path.
+        ``self.mesh_min_component_voxels`` > 0 drops connected pieces of the solid below that many lattice points
+        (floaters; no face labels then)."""
         from ..extract import extract_mesh
         from ..mesh_io import write_ply
         path = self._mesh_path(save_path)
         was_training = self.model.training
         self.model.eval()
         try:
-            m = extract_mesh(self.model, resolution=resolution, threshold=threshold)
+            n_min = int(self.mesh_min_component_voxels)
+            extra = {"min_component_voxels": n_min, "connectivity": self.mesh_connectivity} if n_min > 0 else {}
+            m = extract_mesh(self.model, resolution=resolution, threshold=threshold, **extra)
         finally:
             self.model.train(was_training)
         self.log(f"==> saving mesh to {path} ({m['vertices'].shape[0]} vertices, {m['faces'].shape[0]} faces)")
@@ -1567,7 +1578,10 @@ class Trainer:
         """The labelled scene mesh at ``save_path`` (as ``save_mesh``) and one closed mesh per instance channel k >= 1
         with at least ``min_faces`` faces at ``<save_path minus .ply>_instance_<k>.ply`` (k = the channel, as
         ``masks.write_instance_masks_npz`` numbers them).  The field is evaluated once; only the mesh launches repeat
-        per instance.  -> {"scene": path, "instances": {k: path}}."""
+        per instance.  ``self.mesh_components = "largest"`` / ``"all"`` drops floaters from the label volume first
+        (``extract.filter_components`` with ``self.mesh_connectivity``), so an instance's PLY holds its kept component(s)
+        only.
+        -> {"scene": path, "instances": {k: path}}."""
         from ..extract import mesh_lattices, mesh_of_lattices
         from ..mesh_io import write_ply
         path = self._mesh_path(save_path)
@@ -1575,7 +1589,9 @@ class Trainer:
         was_training = self.model.training
         self.model.eval()
         try:
-            lat = mesh_lattices(self.model, resolution=resolution, threshold=threshold, labels=True, colors=True)
+            extra = ({"components": self.mesh_components, "connectivity": self.mesh_connectivity}
+                     if self.mesh_components is not None else {})
+            lat = mesh_lattices(self.model, resolution=resolution, threshold=threshold, labels=True, colors=True, **extra)
             scene = mesh_of_lattices(lat)
             written = {"scene": write_ply(path, scene["vertices"], scene["faces"], scene["colors"], scene["face_labels"]),
                        "instances": {}}
