@@ -16,6 +16,8 @@ point, colour net once per view direction; ``density`` / ``color`` for non-stand
 because the reference extractor is unseen: voxel-CENTRE positions; rgb = mean over 4 fixed view
 directions (the tetrahedron (1,1,1), (1,-1,-1), (-1,1,-1), (-1,-1,1), normalised).
 """
+import contextlib
+
 import numpy as np
 import torch
 
@@ -47,7 +49,7 @@ def lattice_axes(bbox_min, bbox_max, res, device):
 _AXES_CACHE = {}
 
 
-def _cached_axes(bbox_min, bbox_max, res, device):
+def cached_axes(bbox_min, bbox_max, res, device):
     """``lattice_axes`` kept per (box, resolution, device): a scene is extracted with one lattice, and the upload of a
     fresh one is a synchronous host-to-device copy in front of every extraction."""
     key = (tuple(float(v) for v in bbox_min), tuple(float(v) for v in bbox_max), tuple(int(v) for v in res), str(device))
@@ -66,49 +68,106 @@ def lattice(bbox_min, bbox_max, res, device):
     return torch.stack([ww.reshape(-1), ll.reshape(-1), hh.reshape(-1)], -1)
 
 
-@torch.no_grad()
-def extract_rgbsigma(model, bbox_min=None, bbox_max=None, max_side=160, res=None, chunk=1 << 22):
-    """-> (rgbsigma float32 [W,L,H,4] on the model's device, res int64[3]).  Channel 3 = log(sigma)."""
+def _resolve_lattice(model, bbox_min, bbox_max, max_side, res, axes=False):
+    """The lattice of an extraction call: -> (the model's device, bbox_min, bbox_max float32 [3] (default
+    [-bound, bound]^3), res int64 [3] (default ``grid_resolution`` with ``max_side``), ``cached_axes`` of it or None)."""
     dev = next(model.parameters()).device
     b = float(model.bound)
     bbox_min = np.asarray([-b, -b, -b] if bbox_min is None else bbox_min, dtype=np.float32)
     bbox_max = np.asarray([b, b, b] if bbox_max is None else bbox_max, dtype=np.float32)
     res = grid_resolution(bbox_min, bbox_max, max_side) if res is None else np.asarray(res, dtype=np.int64)
-    cached = getattr(model, "_view_dirs_dev", None)     # the four fixed directions and their SH rows, uploaded once
-    if cached is None or cached[0].device != dev:
-        d = torch.from_numpy(VIEW_DIRS).to(dev)
+    return dev, bbox_min, bbox_max, res, cached_axes(bbox_min, bbox_max, res, dev) if axes else None
+
+
+def view_dirs(model, device):
+    """``VIEW_DIRS`` on ``device`` and their SH rows (``model.encoder_dir``; None for a model without one), uploaded once
+    and kept on the model: -> (dirs float32 [4, 3], sh [4, 16] / None)."""
+    cached = getattr(model, "_view_dirs_dev", None)
+    if cached is None or cached[0].device != device:
+        d = torch.from_numpy(VIEW_DIRS).to(device)
         cached = model._view_dirs_dev = (d, model.encoder_dir(d).contiguous() if hasattr(model, "encoder_dir") else None)
-    dirs = cached[0]
-    if hasattr(model, "forward_lattice"):
-        # one launch for the whole lattice, from its three coordinate axes (no [W*L*H, 3] point tensor), walked in
-        # runs along W: 160^3 in 1.4 ms instead of 2.8 (profiles/r04_NOTES.txt 6)
-        was_training = model.training
-        model.eval()
-        sh = cached[1]
-        # the density logit's lower clamp (log 1e-30, as on the point-list path) is applied inside the launch
-        fused = model.forward_lattice(_cached_axes(bbox_min, bbox_max, res, dev), dirs, logit_min=float(np.log(1e-30)), sh=sh)
-        model.train(was_training)
-        if fused is not None:
-            return fused, res
-    pts = lattice(bbox_min, bbox_max, res, dev)
-    out = torch.empty(pts.shape[0], 4, dtype=torch.float32, device=dev)
+    return cached
+
+
+@contextlib.contextmanager
+def eval_mode(model):
+    """The model in eval mode inside the block, its previous mode restored on any exit."""
     was_training = model.training
     model.eval()
-    for s in range(0, pts.shape[0], chunk):
-        x = pts[s:s + chunk].clamp(-b, b)
-        fused = model.forward_dirs(x, dirs) if hasattr(model, "forward_dirs") else None
-        if fused is not None:                  # one launch: gather + sigma net once, colour net per direction
-            out[s:s + chunk] = fused
-            out[s:s + chunk, 3].clamp_(min=float(np.log(1e-30)))
+    try:
+        yield
+    finally:
+        model.train(was_training)
+
+
+LOGIT_MIN = float(np.log(1e-30))      # floor of the density logit, log(sigma.clamp_min(1e-30)), on every path
+LABEL_EMPTY = 255                     # label of an unoccupied voxel
+
+
+def sweep_lattice(model, bbox_min, bbox_max, res, chunk, want_rgb=False, thresh=None, forward_dirs=False):
+    """The composable form of the lattice launches, with their semantics, over chunks of points: voxel centres clamped to
+    [-bound, bound], ``density()`` once per chunk.  -> (logit, rgb, labels, confidence) over [W, L, H]: the density logit;
+    with ``want_rgb`` (else None) float32 [W, L, H, 4], channels 0..2 = ``color()`` averaged over ``VIEW_DIRS``, channel 3
+    = 0, left to the caller; with ``thresh`` (else None) uint8 labels and float32 confidence: a point is occupied when
+    density_scale * sigma >= thresh and then carries the arg-max over the K real channels of ``instance()`` (torch.argmax:
+    lowest on ties) and its softmax probability, ``LABEL_EMPTY`` / 0 otherwise; ``instance()`` is not called for a chunk
+    without an occupied point.  ``forward_dirs`` (rgb without labels): a chunk goes through ``model.forward_dirs`` - one
+    launch: gather + sigma net once, colour net per direction - when that exists and answers."""
+    dev = next(model.parameters()).device
+    b = float(model.bound)
+    W, L, H = (int(v) for v in res)
+    pts = lattice(bbox_min, bbox_max, res, dev)
+    N = pts.shape[0]
+    logit = torch.empty(N, dtype=torch.float32, device=dev)
+    rgb = torch.zeros(N, 4, dtype=torch.float32, device=dev) if want_rgb else None
+    dirs = view_dirs(model, dev)[0] if want_rgb else None
+    labels = torch.full((N,), LABEL_EMPTY, dtype=torch.uint8, device=dev) if thresh is not None else None
+    conf = torch.zeros(N, dtype=torch.float32, device=dev) if thresh is not None else None
+    forward_dirs = forward_dirs and hasattr(model, "forward_dirs")
+    for s in range(0, N, chunk):
+        x = pts[s:s + chunk].clamp(-b, b).contiguous()
+        fused = model.forward_dirs(x, dirs) if forward_dirs else None
+        if fused is not None:
+            rgb[s:s + chunk, :3] = fused[:, :3]
+            logit[s:s + chunk] = fused[:, 3].clamp(min=LOGIT_MIN)
             continue
         den = model.density(x)
-        rgb = torch.zeros(x.shape[0], 3, dtype=torch.float32, device=dev)
-        for v in range(dirs.shape[0]):
-            rgb += model.color(x, dirs[v].expand(x.shape[0], 3).contiguous(), geo_feat=den["geo_feat"])
-        out[s:s + chunk, :3] = rgb / dirs.shape[0]
-        out[s:s + chunk, 3] = torch.log(den["sigma"].clamp_min(1e-30))
-    model.train(was_training)
-    return out.view(int(res[0]), int(res[1]), int(res[2]), 4), res
+        logit[s:s + chunk] = torch.log(den["sigma"].clamp_min(1e-30))
+        if want_rgb:
+            acc = torch.zeros(x.shape[0], 3, dtype=torch.float32, device=dev)
+            for v in range(dirs.shape[0]):
+                acc += model.color(x, dirs[v].expand(x.shape[0], 3).contiguous(), geo_feat=den["geo_feat"])
+            rgb[s:s + chunk, :3] = acc / dirs.shape[0]
+        if thresh is None:
+            continue
+        occ = den["sigma"] * model.density_scale >= thresh
+        if not bool(occ.any()):
+            continue
+        logits = model.instance(x)[:, :model.num_instances].float()       # the K real channels only
+        mx, arg = logits.amax(1), torch.argmax(logits, 1)
+        c = 1.0 / torch.exp(logits - mx[:, None]).sum(1)
+        labels[s:s + chunk] = torch.where(occ, arg.to(torch.uint8), torch.full_like(labels[s:s + chunk], LABEL_EMPTY))
+        conf[s:s + chunk] = torch.where(occ, c, torch.zeros_like(c))
+    return tuple(None if t is None else t.view(W, L, H, *t.shape[1:]) for t in (logit, rgb, labels, conf))
+
+
+@torch.no_grad()
+def extract_rgbsigma(model, bbox_min=None, bbox_max=None, max_side=160, res=None, chunk=1 << 22):
+    """-> (rgbsigma float32 [W,L,H,4] on the model's device, res int64[3]).  Channel 3 = log(sigma)."""
+    lattice_launch = hasattr(model, "forward_lattice")
+    dev, bbox_min, bbox_max, res, axes = _resolve_lattice(model, bbox_min, bbox_max, max_side, res, axes=lattice_launch)
+    with eval_mode(model):
+        if lattice_launch:
+            # one launch for the whole lattice, from its three coordinate axes (no [W*L*H, 3] point tensor), walked in
+            # runs along W: 160^3 in 1.4 ms instead of 2.8 (profiles/r04_NOTES.txt 6); the density logit's lower clamp
+            # (as on the point-list path) is applied inside the launch
+            dirs, sh = view_dirs(model, dev)
+            fused = model.forward_lattice(axes, dirs, logit_min=LOGIT_MIN, sh=sh)
+            if fused is not None:
+                return fused, res
+        logit, out, _, _ = sweep_lattice(model, bbox_min, bbox_max, res, chunk, want_rgb=True, forward_dirs=True)
+    out[..., 3] = logit
+    return out, res
 
 
 def write_features_npz(path, rgbsigma, bbox_min, bbox_max, scale=1.0, offset=(0.0, 0.0, 0.0), from_mitsuba=False,
@@ -140,9 +199,6 @@ def write_features_npz(path, rgbsigma, bbox_min, bbox_max, scale=1.0, offset=(0.
 
 
 # ---- 3-D instance masks of a trained instance field ---------------------------------------------------------------
-LABEL_EMPTY = 255        # label of an unoccupied voxel
-
-
 def volume_stats(labels, confidence, K):
     """Per-channel statistics of a label volume (uint8 [W, L, H], ``LABEL_EMPTY`` = unoccupied): -> (counts int64 [K],
     boxes int64 [K, 6] = inclusive voxel-index bounds (min iw, il, ih, max iw, il, ih; -1 for an empty channel),
@@ -240,11 +296,13 @@ def _label_composable(labels, connectivity):
     return torch.where(live, parent, torch.full_like(parent, -1)).to(torch.int32).view(W, L, H)
 
 
-def _components_workspace(lib, W, L, H, dev):
+def _workspace(nbytes, what, dtype, dev):
+    """The caller-owned workspace of a library call, from the answer of its ``*_workspace_bytes`` export (negative: the
+    export's error, raised as ``what``): -> (tensor of ``dtype``, nbytes)."""
     from . import _lib
-    nbytes = int(lib.inr_components_workspace_bytes(W, L, H))
-    _lib.check(min(nbytes, 0), "components_workspace_bytes")
-    return torch.empty(nbytes // 8, dtype=torch.int64, device=dev), nbytes
+    nbytes = int(nbytes)
+    _lib.check(min(nbytes, 0), what)
+    return torch.empty(nbytes // dtype.itemsize, dtype=dtype, device=dev), nbytes
 
 
 def _label_hip(labels, connectivity):
@@ -252,7 +310,8 @@ def _label_hip(labels, connectivity):
     lib = _lib.load()
     W, L, H = (int(v) for v in labels.shape)
     labels = labels.contiguous()
-    ws, nbytes = _components_workspace(lib, W, L, H, labels.device)
+    ws, nbytes = _workspace(lib.inr_components_workspace_bytes(W, L, H), "components_workspace_bytes", torch.int64,
+                            labels.device)
     roots = torch.empty(W, L, H, dtype=torch.int32, device=labels.device)
     _lib.check(lib.inr_components_label(_lib.ptr(labels, torch.uint8, "labels"), W, L, H, int(connectivity), _lib.ptr(ws),
                                         nbytes, _lib.ptr(roots), _lib.stream_ptr()), "components_label")
@@ -351,29 +410,6 @@ def filter_components(labels, confidence=None, K=None, connectivity=6, keep="lar
             "kept_root": kept_root}
 
 
-def _instances_composable(model, bbox_min, bbox_max, res, sigma_thresh, chunk):
-    """The composable form of the fused launch, with its semantics: voxel centres clamped to [-bound, bound], occupied
-    when density_scale * sigma >= sigma_thresh, arg-max over the K real channels (torch.argmax: lowest on ties), max-softmax
-    confidence, ``LABEL_EMPTY`` / 0 elsewhere.  ``density()`` and ``instance()`` per chunk of points."""
-    dev = next(model.parameters()).device
-    b = float(model.bound)
-    pts = lattice(bbox_min, bbox_max, res, dev)
-    labels = torch.full((pts.shape[0],), LABEL_EMPTY, dtype=torch.uint8, device=dev)
-    conf = torch.zeros(pts.shape[0], dtype=torch.float32, device=dev)
-    for s in range(0, pts.shape[0], chunk):
-        x = pts[s:s + chunk].clamp(-b, b).contiguous()
-        occ = model.density(x)["sigma"] * model.density_scale >= sigma_thresh
-        if not bool(occ.any()):
-            continue
-        logits = model.instance(x)[:, :model.num_instances].float()       # the K real channels only
-        mx, arg = logits.amax(1), torch.argmax(logits, 1)
-        c = 1.0 / torch.exp(logits - mx[:, None]).sum(1)
-        labels[s:s + chunk] = torch.where(occ, arg.to(torch.uint8), torch.full_like(labels[s:s + chunk], LABEL_EMPTY))
-        conf[s:s + chunk] = torch.where(occ, c, torch.zeros_like(c))
-    W, L, H = (int(v) for v in res)
-    return labels.view(W, L, H), conf.view(W, L, H)
-
-
 @torch.no_grad()
 def extract_instances(model, bbox_min=None, bbox_max=None, max_side=160, res=None, sigma_thresh=None, fused=True,
                       chunk=1 << 20, components=None, connectivity=6, min_component_voxels=1):
@@ -400,25 +436,16 @@ def extract_instances(model, bbox_min=None, bbox_max=None, max_side=160, res=Non
         raise ValueError('extract_instances: components must be None, "largest" or "all"')
     if not getattr(model, "num_instances", 0):
         raise ValueError("extract_instances: the model has no instance head (num_instances = 0)")
-    dev = next(model.parameters()).device
-    b = float(model.bound)
-    bbox_min = np.asarray([-b, -b, -b] if bbox_min is None else bbox_min, dtype=np.float32)
-    bbox_max = np.asarray([b, b, b] if bbox_max is None else bbox_max, dtype=np.float32)
-    res = grid_resolution(bbox_min, bbox_max, max_side) if res is None else np.asarray(res, dtype=np.int64)
+    lattice_launch = fused and hasattr(model, "instance_lattice")
+    _, bbox_min, bbox_max, res, axes = _resolve_lattice(model, bbox_min, bbox_max, max_side, res, axes=lattice_launch)
     thresh = float(model.density_thresh if sigma_thresh is None else sigma_thresh)
     K = int(model.num_instances)
     if K >= LABEL_EMPTY:
         raise ValueError(f"extract_instances: {K} instance channels do not fit the uint8 labels (at most {LABEL_EMPTY - 1})")
-    was_training = model.training
-    model.eval()
-    try:
-        out = None
-        if fused and hasattr(model, "instance_lattice"):
-            out = model.instance_lattice(_cached_axes(bbox_min, bbox_max, res, dev), thresh)
+    with eval_mode(model):
+        out = model.instance_lattice(axes, thresh) if lattice_launch else None
         if out is None:
-            out = _instances_composable(model, bbox_min, bbox_max, res, thresh, chunk)
-    finally:
-        model.train(was_training)
+            out = sweep_lattice(model, bbox_min, bbox_max, res, chunk, thresh=thresh)[2:]
     labels, conf = out
     extra = {}
     if components is not None:
@@ -474,9 +501,7 @@ def mesh_from_lattice(field, iso, axes, ext, labels=None, select=-1, rgb=None, f
     if [int(a.shape[0]) for a in ax] != [W, L, H]:
         raise RuntimeError("mesh_from_lattice: the axes do not match the field")
     cap = 1 if cap else 0
-    nbytes = int(lib.inr_mesh_workspace_bytes(W, L, H, cap))
-    _lib.check(min(nbytes, 0), "mesh_workspace_bytes")
-    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    ws, nbytes = _workspace(lib.inr_mesh_workspace_bytes(W, L, H, cap), "mesh_workspace_bytes", torch.int32, dev)
     counts = torch.empty(2, dtype=torch.int32, device=dev)
     P = _lib.ptr
     fptr, lptr = _lib.c_void_p(field.data_ptr()), P(labels, torch.uint8, "labels", allow_none=True)
@@ -495,26 +520,21 @@ def mesh_from_lattice(field, iso, axes, ext, labels=None, select=-1, rgb=None, f
     return {"vertices": vertices, "faces": faces, "colors": colors, "face_labels": flab}
 
 
-def _mesh_lattices_composable(model, bbox_min, bbox_max, res, thresh, need_labels, need_rgb, chunk=1 << 20):
-    """The lattices of ``mesh_lattices`` through ``density()`` / ``color()`` / ``instance()`` over chunks of points."""
-    dev = next(model.parameters()).device
-    b = float(model.bound)
-    W, L, H = (int(v) for v in res)
-    pts = lattice(bbox_min, bbox_max, res, dev)
-    logit = torch.empty(pts.shape[0], dtype=torch.float32, device=dev)
-    rgbs = torch.zeros(W, L, H, 4, dtype=torch.float32, device=dev) if need_rgb else None
-    dirs = torch.from_numpy(VIEW_DIRS).to(dev)
-    for s in range(0, pts.shape[0], chunk):
-        x = pts[s:s + chunk].clamp(-b, b).contiguous()
-        den = model.density(x)
-        logit[s:s + chunk] = torch.log(den["sigma"].clamp_min(1e-30))
-        if need_rgb:
-            acc = torch.zeros(x.shape[0], 3, dtype=torch.float32, device=dev)
-            for v in range(dirs.shape[0]):
-                acc += model.color(x, dirs[v].expand(x.shape[0], 3).contiguous(), geo_feat=den["geo_feat"])
-            rgbs.view(-1, 4)[s:s + chunk, :3] = acc / dirs.shape[0]
-    labels = _instances_composable(model, bbox_min, bbox_max, res, thresh, chunk)[0] if need_labels else None
-    return logit.view(W, L, H), labels, rgbs
+def _mesh_lattices_fused(model, axes, thresh, labels, colors):
+    """``mesh_lattices`` through the lattice launches: -> (field, labels, rgb).  field is None when a launch the call needs
+    is missing or answered None; rgb is None also when the call did not need that launch."""
+    field = lab = rgb = None
+    if labels:                                   # labels and field from one launch
+        out = model.instance_lattice(axes, thresh, want_logit=True) if hasattr(model, "instance_lattice") else None
+        if out is None:
+            return None, None, None
+        lab, _, field = out
+    if (colors or not labels) and hasattr(model, "forward_lattice"):
+        dirs, sh = view_dirs(model, axes[0].device)
+        rgb = model.forward_lattice(axes, dirs, logit_min=LOGIT_MIN, sh=sh)
+        if not labels and rgb is not None:
+            field = rgb[..., 3]                  # channel 3 as a stride-4 view, read in place by the mesh kernels
+    return field, lab, rgb
 
 
 @torch.no_grad()
@@ -529,39 +549,19 @@ def mesh_lattices(model, bbox_min=None, bbox_max=None, resolution=256, res=None,
         raise ValueError('mesh_lattices: components must be None, "largest" or "all"')
     if components is not None and not labels:
         raise ValueError("mesh_lattices: components filters the label volume and needs labels=True")
-    dev = next(model.parameters()).device
-    if dev.type != "cuda":
+    if next(model.parameters()).device.type != "cuda":
         raise RuntimeError("extract_mesh: the model must be on a GPU (the HIP path has no CPU fallback)")
     if not float(threshold) > 0:
         raise ValueError("extract_mesh: threshold must be > 0 (the surface is density_scale * sigma = threshold)")
     if labels and not getattr(model, "num_instances", 0):
         raise ValueError("extract_mesh: the model has no instance head (num_instances = 0)")
-    b = float(model.bound)
-    bbox_min = np.asarray([-b, -b, -b] if bbox_min is None else bbox_min, dtype=np.float32)
-    bbox_max = np.asarray([b, b, b] if bbox_max is None else bbox_max, dtype=np.float32)
-    res = grid_resolution(bbox_min, bbox_max, resolution) if res is None else np.asarray(res, dtype=np.int64)
+    _, bbox_min, bbox_max, res, axes = _resolve_lattice(model, bbox_min, bbox_max, resolution, res, axes=True)
     iso = float(np.log(np.float32(threshold) / np.float32(getattr(model, "density_scale", 1.0)), dtype=np.float32))
-    axes = _cached_axes(bbox_min, bbox_max, res, dev)
-    was_training = model.training
-    model.eval()
-    try:
-        field = lab = rgb = None
-        if fused and labels and hasattr(model, "instance_lattice"):
-            out = model.instance_lattice(axes, float(threshold), want_logit=True)
-            if out is not None:
-                lab, _, field = out
-        if fused and (colors or not labels) and hasattr(model, "forward_lattice") and (field is not None or not labels):
-            cached = getattr(model, "_view_dirs_dev", None)
-            if cached is None or cached[0].device != dev:
-                d = torch.from_numpy(VIEW_DIRS).to(dev)
-                cached = model._view_dirs_dev = (d, model.encoder_dir(d).contiguous() if hasattr(model, "encoder_dir") else None)
-            rgb = model.forward_lattice(axes, cached[0], logit_min=float(np.log(1e-30)), sh=cached[1])
-            if rgb is not None and field is None:
-                field = rgb[..., 3]
-        if field is None or (colors and rgb is None):
-            field, lab, rgb = _mesh_lattices_composable(model, bbox_min, bbox_max, res, float(threshold), labels, colors)
-    finally:
-        model.train(was_training)
+    with eval_mode(model):
+        field, lab, rgb = _mesh_lattices_fused(model, axes, float(threshold), labels, colors) if fused else (None,) * 3
+        if field is None or (colors and rgb is None):            # all of it from the sweep: no mixing of the two paths
+            field, rgb, lab, _ = sweep_lattice(model, bbox_min, bbox_max, res, 1 << 20, want_rgb=colors,
+                                        thresh=float(threshold) if labels else None)
     if components is not None and lab is not None:
         lab = filter_components(lab, None, K=int(model.num_instances), connectivity=connectivity, keep=components,
                                 min_voxels=min_component_voxels, skip_background=True, fused=fused)["labels"]

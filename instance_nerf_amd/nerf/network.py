@@ -817,6 +817,19 @@ class NeRFNetwork(NeRFRenderer):
                                         ptr(out, allow_none=M == 0), stream_ptr()), "nerf_forward_dirs")
         return out
 
+    def _lattice_args(self, axes):
+        """-> ((W, L, H), ax, head) of the lattice ``axes``: ``ax`` the float32 axes (their device is the outputs'), ``head``
+        the arguments every lattice launch opens with (pointers into ``ax``, the sizes, the bound, the NeRF table and
+        its packed weights), None for an empty lattice, which launches nothing."""
+        ax = [a.contiguous().float() for a in axes]
+        W, L, H = (int(a.shape[0]) for a in ax)
+        if W * L * H == 0:
+            return (W, L, H), ax, None
+        return (W, L, H), ax, (ptr(ax[0], torch.float32, "ax_w"), ptr(ax[1], torch.float32, "ax_l"),
+                               ptr(ax[2], torch.float32, "ax_h"), W, L, H, float(self.bound),
+                               ptr(self.encoder.embeddings.data, torch.float32), self.encoder.desc,
+                               ptr(self._packed_weights("nerf")))
+
     @torch.no_grad()
     def forward_lattice(self, axes, dirs, logit_min=float("-inf"), sh=None):
         """``forward_dirs`` for the lattice ``axes = (ax_w [W], ax_l [L], ax_h [H])`` (float32, on the device): -> float
@@ -827,18 +840,13 @@ class NeRFNetwork(NeRFRenderer):
         if not self._fusable:
             return None
         lib = _lib.load()
-        ax = [a.contiguous().float() for a in axes]
-        W, L, H = (int(a.shape[0]) for a in ax)
-        D = dirs.shape[0]
+        shape, ax, head = self._lattice_args(axes)
         if sh is None:
             sh = self.encoder_dir(dirs.to(ax[0].device).contiguous().float()).contiguous()  # [D,16] (HIP SH kernel)
-        out = torch.empty(W, L, H, 4, dtype=torch.float32, device=ax[0].device)
-        if W * L * H:
-            check(lib.inr_nerf_forward_lattice(ptr(ax[0], torch.float32, "ax_w"), ptr(ax[1], torch.float32, "ax_l"),
-                                               ptr(ax[2], torch.float32, "ax_h"), W, L, H, float(self.bound),
-                                               ptr(self.encoder.embeddings.data, torch.float32), self.encoder.desc,
-                                               ptr(self._packed_weights("nerf")), ptr(sh, torch.float32, "sh_dirs"), D,
-                                               float(logit_min), ptr(out), stream_ptr()), "nerf_forward_lattice")
+        out = torch.empty(*shape, 4, dtype=torch.float32, device=ax[0].device)
+        if head is not None:
+            check(lib.inr_nerf_forward_lattice(*head, ptr(sh, torch.float32, "sh_dirs"), dirs.shape[0], float(logit_min),
+                                               ptr(out), stream_ptr()), "nerf_forward_lattice")
         return out
 
     @torch.no_grad()
@@ -852,18 +860,14 @@ class NeRFNetwork(NeRFRenderer):
         if not (self._fusable and self.num_instances and self._fusable_inst):
             return None
         lib = _lib.load()
-        ax = [a.contiguous().float() for a in axes]
-        W, L, H = (int(a.shape[0]) for a in ax)
+        shape, ax, head = self._lattice_args(axes)
         dev = ax[0].device
-        labels = torch.empty(W, L, H, dtype=torch.uint8, device=dev)
-        conf = torch.empty(W, L, H, dtype=torch.float32, device=dev)
-        logit = torch.empty(W, L, H, dtype=torch.float32, device=dev) if want_logit else None
-        if W * L * H:
-            check(lib.inr_instance_lattice(ptr(ax[0], torch.float32, "ax_w"), ptr(ax[1], torch.float32, "ax_l"),
-                                           ptr(ax[2], torch.float32, "ax_h"), W, L, H, float(self.bound),
-                                           ptr(self.encoder.embeddings.data, torch.float32), self.encoder.desc,
-                                           ptr(self._packed_weights("nerf")), float(self.density_scale),
-                                           float(sigma_thresh), ptr(self.instance_encoder.embeddings.data, torch.float32),
+        labels = torch.empty(shape, dtype=torch.uint8, device=dev)
+        conf = torch.empty(shape, dtype=torch.float32, device=dev)
+        logit = torch.empty(shape, dtype=torch.float32, device=dev) if want_logit else None
+        if head is not None:
+            check(lib.inr_instance_lattice(*head, float(self.density_scale), float(sigma_thresh),
+                                           ptr(self.instance_encoder.embeddings.data, torch.float32),
                                            self.instance_encoder.desc, ptr(self._packed_weights("instance")),
                                            self.num_instances, ptr(labels, torch.uint8), ptr(conf),
                                            ptr(logit, allow_none=True), stream_ptr()), "instance_lattice")

@@ -1535,13 +1535,7 @@ class Trainer:
         write_kw = {k: extract_kwargs.pop(k) for k in ("labels", "min_voxels") if k in extract_kwargs}
         save_path = save_path or os.path.join(self.workspace or ".", "masks")
         path = os.path.join(save_path, f"{name or self.name}.npz")
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            result = extract_instances(self.model, **extract_kwargs)
-        finally:
-            self.model.train(was_training)
-        return write_instance_masks_npz(path, result, **write_kw)
+        return write_instance_masks_npz(path, extract_instances(self.model, **extract_kwargs), **write_kw)
 
     def _mesh_path(self, save_path):
         return save_path or os.path.join(self.workspace or ".", "meshes", f"{self.name}_{self.epoch}.ply")
@@ -1563,14 +1557,9 @@ class Trainer:
         from ..extract import extract_mesh
         from ..mesh_io import write_ply
         path = self._mesh_path(save_path)
-        was_training = self.model.training
-        self.model.eval()
-        try:
-            n_min = int(self.mesh_min_component_voxels)
-            extra = {"min_component_voxels": n_min, "connectivity": self.mesh_connectivity} if n_min > 0 else {}
-            m = extract_mesh(self.model, resolution=resolution, threshold=threshold, **extra)
-        finally:
-            self.model.train(was_training)
+        n_min = int(self.mesh_min_component_voxels)
+        extra = {"min_component_voxels": n_min, "connectivity": self.mesh_connectivity} if n_min > 0 else {}
+        m = extract_mesh(self.model, resolution=resolution, threshold=threshold, **extra)
         self.log(f"==> saving mesh to {path} ({m['vertices'].shape[0]} vertices, {m['faces'].shape[0]} faces)")
         return write_ply(path, m["vertices"], m["faces"], m["colors"], m["face_labels"])
 
@@ -1582,13 +1571,11 @@ class Trainer:
         (``extract.filter_components`` with ``self.mesh_connectivity``), so an instance's PLY holds its kept component(s)
         only.
         -> {"scene": path, "instances": {k: path}}."""
-        from ..extract import mesh_lattices, mesh_of_lattices
+        from ..extract import eval_mode, mesh_lattices, mesh_of_lattices
         from ..mesh_io import write_ply
         path = self._mesh_path(save_path)
         stem = path[:-4] if path.lower().endswith(".ply") else path
-        was_training = self.model.training
-        self.model.eval()
-        try:
+        with eval_mode(self.model):
             extra = ({"components": self.mesh_components, "connectivity": self.mesh_connectivity}
                      if self.mesh_components is not None else {})
             lat = mesh_lattices(self.model, resolution=resolution, threshold=threshold, labels=True, colors=True, **extra)
@@ -1602,8 +1589,6 @@ class Trainer:
                 m = mesh_of_lattices(lat, instance=k)
                 if m["faces"].shape[0] >= max(int(min_faces), 1):
                     written["instances"][k] = write_ply(f"{stem}_instance_{k}.ply", m["vertices"], m["faces"], m["colors"])
-        finally:
-            self.model.train(was_training)
         return written
 
     # -- checkpoint (upstream keys: epoch, global_step, stats, model, optimizer, lr_scheduler, ema, mean_count, mean_density)

@@ -216,6 +216,28 @@ def test_fused_and_composable_paths_give_the_same_faces():
             assert (a["colors"] - b["colors"]).abs().max() < 1e-3
 
 
+def test_composable_lattices_with_labels_and_colours():
+    """``labels=True`` with ``fused=False``: labels, field and colours of one sweep, against ``extract_instances`` and the
+    model's own ``density()`` / ``color()`` on the clamped lattice."""
+    from instance_nerf_amd import extract
+    K = 16
+    net = _net(_params(K, seed=3), K)
+    thresh = _quiet_threshold(net)
+    lat = extract.mesh_lattices(net, BOX_MIN, BOX_MAX, res=RES, threshold=thresh, labels=True, colors=True, fused=False)
+    ref = extract.extract_instances(net, BOX_MIN, BOX_MAX, res=RES, sigma_thresh=thresh, fused=False)
+    assert lat["labels"].dtype == torch.uint8 and torch.equal(lat["labels"], ref["labels"])
+    pts = extract.lattice(BOX_MIN, BOX_MAX, RES, DEV).clamp(-1.0, 1.0)
+    with torch.no_grad():
+        den = net.density(pts)
+        dirs = torch.from_numpy(extract.VIEW_DIRS).to(DEV)
+        rgb = sum(net.color(pts, dirs[v].expand(pts.shape[0], 3).contiguous(), geo_feat=den["geo_feat"]) for v in range(4)) / 4
+    assert torch.equal(lat["field"], torch.log(den["sigma"].clamp_min(1e-30)).view(*RES.tolist()))
+    assert (lat["rgb"][..., :3] - rgb.view(*RES.tolist(), 3)).abs().max() <= 1e-6
+    k = int(torch.bincount(ref["labels"].reshape(-1).long(), minlength=256)[:K].argmax())
+    one = extract.extract_mesh(net, BOX_MIN, BOX_MAX, res=RES, threshold=thresh, instance=k, fused=False)
+    assert one["faces"].shape[0] >= 1 and mr.is_closed(one["faces"].cpu().numpy())
+
+
 def test_threshold_above_every_sigma_gives_an_empty_mesh_and_a_valid_ply(tmp_path):
     from instance_nerf_amd import extract, mesh_io
     net = _net(_params(16, seed=3), 16)

@@ -126,7 +126,7 @@ def main():
         labels, conf = base["labels"], base["confidence"]
         W, L, H = (int(v) for v in labels.shape)
         n = W * L * H
-        axes = extract._cached_axes(np.float32([-1, -1, -1]), np.float32([1, 1, 1]), base["res"], DEV)
+        axes = extract.cached_axes(np.float32([-1, -1, -1]), np.float32([1, 1, 1]), base["res"], DEV)
         lattice = timed(lambda: net.instance_lattice(axes, 10.0), 2, a.repeats)
         nbytes = int(lib.inr_components_workspace_bytes(W, L, H))
         ws = torch.empty(nbytes // 8, dtype=torch.int64, device=DEV)

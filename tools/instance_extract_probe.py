@@ -99,7 +99,7 @@ def main():
         n_runs = int(run_live.numel())
         n_live = int(run_live.sum())
         vox_live = int((run_live.unsqueeze(1).expand(-1, 16, -1, -1).reshape(Wp, L, H)[:W]).sum())
-        axes = extract._cached_axes(np.float32([-1, -1, -1]), np.float32([1, 1, 1]), res, DEV)
+        axes = extract.cached_axes(np.float32([-1, -1, -1]), np.float32([1, 1, 1]), res, DEV)
         fused = timed(lambda: extract.extract_instances(m, max_side=a.max_side), 2, a.repeats)
         lattice_only = timed(lambda: m.instance_lattice(axes, 10.0), 2, a.repeats)
         comp = timed(lambda: extract.extract_instances(m, max_side=a.max_side, fused=False), 1, max(3, a.repeats // 3))

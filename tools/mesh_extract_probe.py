@@ -15,7 +15,6 @@ import os
 import sys
 import tempfile
 
-import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -88,9 +87,9 @@ def main():
     for R in (160, 256):
         lat = extract.mesh_lattices(net, resolution=R, threshold=10.0, labels=True, colors=True)
         axes = lat["axes"]
-        cached = net._view_dirs_dev
+        dirs, sh = extract.view_dirs(net, DEV)
         t_inst = timed(lambda: net.instance_lattice(axes, 10.0, want_logit=True), 2, a.repeats)
-        t_rgb = timed(lambda: net.forward_lattice(axes, cached[0], logit_min=float(np.log(1e-30)), sh=cached[1]), 2, a.repeats)
+        t_rgb = timed(lambda: net.forward_lattice(axes, dirs, logit_min=extract.LOGIT_MIN, sh=sh), 2, a.repeats)
         count, emit, V, F = mesh_calls(lat, -1, True, True)
         t_count, t_emit = timed(count, 2, a.repeats), timed(emit, 2, a.repeats)
         t_call = timed(lambda: extract.extract_mesh(net, resolution=R, threshold=10.0), 2, a.repeats)
