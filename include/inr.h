@@ -637,6 +637,41 @@ int inr_components_filter(const uint8_t* labels, const int32_t* roots, const flo
                           void* workspace, int64_t workspace_bytes, uint8_t* labels_out, float* confidence_out /*nullable*/,
                           int32_t* n_components, int32_t* kept_voxels, int32_t* kept_root, inr_stream_t s);
 
+/* ---- 2-D mask matching (replaces the reference's CPU script Mask2Former_sample/match_seg.py:94-150, the step between
+ * the 3-D mask projector and the instance stage).  Additive: no version bump.  B views of P = H * W pixels, k candidate
+ * masks in CANDIDATE ORDER (the reference's sorted-file-name order of "<img>_<id>.png"; the caller orders them), nw =
+ * ceil(k / 32) words per pixel: bit j % 32 of words[b][j / 32][p] = candidate j covers pixel p of view b.
+ *
+ * The rule, per view: seg holds -1 (unlabeled), 0 (background) or the RANK 1..S of a segment (dense per view; the
+ * caller ranks the segment ids).  For rank r with area_r = |seg == r| > 0 and every candidate j,
+ *   iou[j] = inter / (area_r + area_j - inter),  inter = |seg == r & m_j|,  area_j = |m_j|,
+ * the counts combined in integers and divided in fp64 (IEEE division: the bits of numpy's np.sum(..) / np.sum(..)).
+ * j* = the FIRST maximum.  The rank is assigned instance_ids[j*] if iou[j*] > iou_thresh (fp64 comparison), else -1;
+ * with k = 0 or area_r = 0 it is assigned -1.  Pixels <= 0 pass through.
+ *
+ * inr_pack_mask_bits: words uint32 [nw, P] of ONE view from the projector's soft sums: clears `words`, then sets bit
+ *   j % 32 of words[j / 32][inds[n]] where soft[n][j] > thresh (NaN: false).  soft float [N, k]; inds int64 [N]
+ *   (nullable = identity) are DISTINCT pixel indices by the caller's contract; one outside [0, P) is skipped.
+ *   1 <= k <= 1024, 0 <= N, 1 <= P, both below 2^31.  One fill and one launch.
+ * inr_match_count: zeroes its outputs, then counts.  seg int32 [B, P]; words uint32 [B, nw, P] (bits at and above k are
+ *   ignored);  seg_area int32 [B, S + 1]: pixels per rank, [b][0] = pixels with seg <= 0;  mask_area int32 [B, k];
+ *   inter int32 [B, S + 1, k], row 0 = the candidate's pixels outside every segment.  A seg value outside [-1, S] is
+ *   counted nowhere and sets status[0] (int32 [1]) to non-zero; otherwise status[0] = 0.  words, mask_area and inter may
+ *   be null when k = 0.  Limits: 1 <= B, 1 <= P, B * P < 2^31, 0 <= S <= 1023, 0 <= k <= 1024; INR_EINVAL beyond.
+ *   Three launches: zero, count (all views and words in one launch; the (S + 1) x 32 counters of a word live in LDS,
+ *   lanes of a wave that hold the same (rank, word) pair are counted once), column sums.
+ * inr_match_assign: with the SAME seg and the counts inr_match_count wrote: assigned int32 [B, S + 1] per the rule
+ *   ([b][0] = 0, unused), then out int32 [B, P] = -1, 0 or assigned[b][seg[p]] (-1 for a value outside [-1, S]).
+ *   iou_thresh: HOST pointer to one double in [0, 1], read before the call returns.  Two launches.
+ * Integer atomics only: two calls give identical bits.                                                             */
+int inr_pack_mask_bits(const float* soft, const int64_t* inds /*nullable*/, int64_t N, int32_t k, float thresh, int64_t P,
+                       uint32_t* words, inr_stream_t s);
+int inr_match_count(const int32_t* seg, const uint32_t* words, int64_t B, int64_t P, int32_t S, int32_t k,
+                    int32_t* seg_area, int32_t* mask_area, int32_t* inter, int32_t* status, inr_stream_t s);
+int inr_match_assign(const int32_t* seg, const int32_t* seg_area, const int32_t* mask_area, const int32_t* inter,
+                     const int32_t* instance_ids, int64_t B, int64_t P, int32_t S, int32_t k,
+                     const double* iou_thresh /*host*/, int32_t* assigned, int32_t* out, inr_stream_t s);
+
 /* ---- 3-D RoIAlign ("next" row f2; replaces roi_align.roi_align.roi_align_3d, the one FFI call in the
  * reference tree: /root/reference/nerf_rcnn/model/utils.py:604-609).  torchvision roi_align semantics
  * (aligned=False, adaptive ceil(roi/out) sampling grid, average) on three axes: x<->W, y<->L, z<->H.

@@ -10,7 +10,12 @@ f4  ``project_3d_masks``: counterpart of the reference's ``scripts/project_3d_ma
     (match_seg.py:55-62,99-102: files ``*_0.png`` are skipped by the consumer).  A pixel belongs to
     instance i when the NeRF-weighted mask value along its ray, sum_s w_s * mask_i(x_s), exceeds
     ``thresh``: the K-channel compositing of the render path with mask_i as the extra channel.
+f5  ``match_masks`` / ``project_and_match`` / ``match_seg_dir``: the matching step between the two, the reference's CPU
+    script Mask2Former_sample/match_seg.py:94-150, on the device (csrc/match.hip): every 2-D segment takes the id of the
+    projected 3-D mask it overlaps best.  ``project_and_match`` feeds the projector's sums to the matcher without leaving
+    the GPU; ``match_seg_dir`` is the drop-in for the script on one scene directory.
 """
+import json
 import os
 import struct
 import zlib
@@ -229,3 +234,320 @@ def write_instance_masks_npz(path, result, labels=None, min_voxels=1):
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     np.savez_compressed(path, masks=masks, scores=out_scores, labels=cls, boxes=out_boxes)
     return path
+
+
+# ---------------------------------------------------------------------------------------- f5
+# The one fact of the reference's class tables (match_seg.py:17-48) that the matching rule uses: the COCO panoptic STUFF
+# classes it maps to NYU40 id 40 = background.  Every other class, things included, keeps its segment.
+BACKGROUND_STUFF = frozenset((
+    "curtain", "door-stuff", "floor-wood", "stairs", "wall-brick", "wall-stone", "wall-tile", "wall-wood", "window-blind",
+    "window-other", "ceiling-merged", "floor-other-merged", "building-other-merged", "wall-other-merged"))
+MATCH_MAX_SEGMENTS, MATCH_MAX_CANDIDATES = 1023, 1024          # include/inr.h: limits of inr_match_count
+_IDENTITY_RANK_MAX = 255        # segment ids up to here are their own ranks (Mask2Former's are 1..~100): no sort needed
+
+
+def convert_segments(panoptic, segments_info, class_names=None):
+    """Panoptic map + segment list of one image -> int32 [H, W] (match_seg.py:65-91): -1 unlabeled (0 in the input),
+    0 background, otherwise the segment's own id.  A segment is background when it is not a thing and its class name is
+    in ``BACKGROUND_STUFF``; ids that occur in the map but not in ``segments_info`` become 0.  Each segment dict carries
+    ``id`` (> 0), ``isthing`` and either ``name`` or ``category_id``; the latter is looked up in ``class_names``, a dict
+    with ``thing_classes`` / ``stuff_classes`` lists or the path of such a json (the user's coco_id_to_name.json).  Host
+    code (numpy).  A negative value in ``panoptic`` raises ValueError."""
+    seg = np.asarray(panoptic)
+    if seg.ndim != 2:
+        raise ValueError(f"panoptic must be [H, W], got shape {seg.shape}")
+    if seg.size and seg.min() < 0:
+        raise ValueError("panoptic holds a negative value (0 = unlabeled, > 0 = segment id)")
+    seg = seg.astype(np.int32)
+    if isinstance(class_names, (str, os.PathLike)):
+        with open(class_names) as f:
+            class_names = json.load(f)
+    out = np.zeros_like(seg)
+    out[seg == 0] = -1
+    for s in segments_info:
+        sid = int(s["id"])
+        if sid <= 0:
+            raise ValueError(f"segment id {sid} must be > 0")
+        name = s.get("name")
+        if name is None:
+            if class_names is None:
+                raise ValueError("a segment without 'name' needs class_names to look its category_id up")
+            name = class_names["thing_classes" if s["isthing"] else "stuff_classes"][int(s["category_id"])]
+        out[seg == sid] = 0 if (not s["isthing"] and name in BACKGROUND_STUFF) else sid
+    return out
+
+
+def candidate_order(instance_ids):
+    """Positions of the candidates in the reference's order: the sorted file names ``<img>_<id>.png`` (match_seg.py:102),
+    which is the string order of ``f"{id}.png"`` - 1 before 12 before 3.  The order decides ties between candidates."""
+    ids = [int(i) for i in instance_ids]
+    return sorted(range(len(ids)), key=lambda i: (f"{ids[i]}.png", i))
+
+
+def select_projections(files, img_name):
+    """The reference's file selection for one image (match_seg.py:99-102,114-117): ``*.png`` with an underscore whose part
+    after the FIRST underscore is not ``0.png``, sorted by name, whose name STARTS with the image's name (so image
+    ``0001`` also takes ``00010_9.png``).  -> (file names, instance ids)."""
+    keep = sorted(f for f in files if f.endswith(".png") and "_" in f and f.split("_")[1] != "0.png")
+    mine = [f for f in keep if f.startswith(img_name)]
+    return mine, [int(f.split("_")[1].split(".")[0]) for f in mine]
+
+
+def pack_mask_bits(proj, device=None):
+    """bool [n, k, H, W] (numpy or tensor) -> int32 tensor [n, ceil(k / 32), H, W] on ``device`` (default: where ``proj``
+    lives): bit j % 32 of word j // 32 = candidate j covers the pixel - the layout ``inr_match_count`` reads (int32 is the
+    storage type, the kernel reads uint32).  ``match_masks`` accepts the result in place of ``proj``."""
+    m = torch.as_tensor(proj)
+    if m.dtype != torch.bool or m.ndim != 4:
+        raise ValueError("proj must be bool [n, k, H, W]")
+    m = m.to(device if device is not None else m.device)
+    n, k, H, W = m.shape
+    out = torch.zeros(n, (k + 31) // 32, H, W, dtype=torch.int32, device=m.device)
+    for v in range(n):                                   # per view: the int64 staging is 32 words per pixel
+        for j in range(out.shape[1]):
+            chunk = m[v, 32 * j:32 * j + 32].to(torch.int64)
+            shifts = torch.arange(chunk.shape[0], device=m.device, dtype=torch.int64).view(-1, 1, 1)
+            w = (chunk << shifts).sum(0)
+            out[v, j] = torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
+    return out
+
+
+def _rank_segments(seg):
+    """int32 tensor [n, P] of converted maps -> (ranks int32 [n, P], S): -1 and 0 pass through, a segment id > 0 becomes
+    its rank 1..S among the ids of ITS view (S = the largest count over the views).  Ids that are small already are their
+    own ranks (a rank without pixels is never assigned).  One read-back (the largest id / S)."""
+    n, P = seg.shape
+    if seg.numel() == 0:
+        return seg, 0
+    if bool((seg < -1).any()):
+        raise ValueError("seg_maps hold a value below -1")
+    top = int(seg.max())
+    if top <= _IDENTITY_RANK_MAX:
+        return seg, max(top, 0)
+    big = top + 1
+    pos = seg > 0
+    view = torch.arange(n, device=seg.device, dtype=torch.int64).view(n, 1).expand(n, P)[pos]
+    uniq, inv = torch.unique(view * big + seg[pos].long(), return_inverse=True)           # sorted: by view, then by id
+    starts = torch.searchsorted(uniq, torch.arange(n + 1, device=seg.device, dtype=torch.int64) * big)
+    ranks = seg.clone()
+    ranks[pos] = (inv - starts[view] + 1).to(torch.int32)
+    return ranks, int((starts[1:] - starts[:-1]).max())
+
+
+def _rank_segments_numpy(seg):
+    """The same on the host for numpy input: np.unique per view."""
+    if seg.size and seg.min() < -1:
+        raise ValueError("seg_maps hold a value below -1")
+    ranks, S = seg.copy(), 0
+    for v in range(seg.shape[0]):
+        pos = seg[v] > 0
+        uniq, inv = np.unique(seg[v][pos], return_inverse=True)
+        ranks[v][pos] = inv.reshape(-1) + 1
+        S = max(S, int(uniq.size))
+    return ranks, S
+
+
+def match_ranked(ranks, words, S, k, instance_ids, iou_thresh=0.05):
+    """The two device calls (include/inr.h, "2-D mask matching") on ranked maps: ranks int32 [n, P] (-1, 0 or a rank
+    1..S), words int32 [n, ceil(k / 32), P] (``pack_mask_bits`` layout; ignored when k = 0), instance_ids int32 tensor [k]
+    in candidate order.  -> int32 [n, P].  One read-back after both calls: a rank outside [-1, S] raises ValueError."""
+    from . import _lib
+    from ._lib import check, ptr, stream_ptr
+    import ctypes
+    n, P = (int(v) for v in ranks.shape)
+    dev = ranks.device
+    lib = _lib.load()
+    nw = (k + 31) // 32
+    if k > 0 and tuple(words.shape) != (n, nw, P):
+        raise ValueError(f"words must be [{n}, {nw}, {P}], got {tuple(words.shape)}")
+    seg_area = torch.empty(n, S + 1, dtype=torch.int32, device=dev)
+    mask_area = torch.empty(n, k, dtype=torch.int32, device=dev)
+    inter = torch.empty(n, S + 1, k, dtype=torch.int32, device=dev)
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    assigned = torch.empty(n, S + 1, dtype=torch.int32, device=dev)
+    out = torch.empty(n, P, dtype=torch.int32, device=dev)
+    none = k == 0
+    check(lib.inr_match_count(ptr(ranks, torch.int32, "ranks"), ptr(None if none else words, torch.int32, "words", allow_none=none),
+                              n, P, S, k, ptr(seg_area), ptr(None if none else mask_area, allow_none=none),
+                              ptr(None if none else inter, allow_none=none), ptr(status), stream_ptr()), "match_count")
+    thresh = ctypes.c_double(float(iou_thresh))
+    check(lib.inr_match_assign(ptr(ranks), ptr(seg_area), ptr(None if none else mask_area, allow_none=none),
+                               ptr(None if none else inter, allow_none=none),
+                               ptr(None if none else instance_ids, torch.int32, "instance_ids", allow_none=none), n, P, S, k,
+                               ctypes.cast(ctypes.pointer(thresh), ctypes.c_void_p), ptr(assigned), ptr(out), stream_ptr()),
+          "match_assign")
+    if int(status) != 0:
+        raise ValueError(f"match: a rank lies outside [-1, {S}]")
+    return out
+
+
+def _match_composable(ranks, proj, words, S, k, ids, iou_thresh):
+    """The rule in plain torch on any device, one view at a time: integer one-hot counts (bincount), fp64 division, first
+    argmax.  Same bits as the fused path; the CPU path and the timing twin."""
+    n, P = ranks.shape
+    dev = ranks.device
+    out = ranks.clone()
+    if bool(((ranks < -1) | (ranks > S)).any()):
+        raise ValueError(f"match: a rank lies outside [-1, {S}]")
+    cols = torch.arange(k, device=dev, dtype=torch.int64)
+    for v in range(n):
+        r = ranks[v].long()
+        row = r.clamp(min=0)
+        seg_area = torch.bincount(row, minlength=S + 1)
+        if k > 0:
+            if proj is not None:
+                m = proj[v].reshape(k, P).t()
+            else:
+                m = ((words[v][cols // 32].long() >> (cols % 32).view(k, 1)) & 1).bool().t()
+            inter = torch.bincount((row.view(P, 1) * k + cols.view(1, k))[m], minlength=(S + 1) * k).view(S + 1, k)
+            mask_area = inter.sum(0)
+            union = seg_area.view(S + 1, 1) + mask_area.view(1, k) - inter
+            iou = torch.where(union > 0, inter.double() / union.clamp(min=1).double(), torch.zeros((), dtype=torch.float64, device=dev))
+            best = iou.max(1).values
+            first = torch.where(iou == best.view(S + 1, 1), cols.view(1, k), k).min(1).values
+            assigned = torch.where((best > float(iou_thresh)) & (seg_area > 0), ids.long()[first], -1)
+        else:
+            assigned = torch.full((S + 1,), -1, dtype=torch.int64, device=dev)
+        out[v] = torch.where(r > 0, assigned[row], r).to(torch.int32)
+    return out
+
+
+@torch.no_grad()
+def match_masks(seg_maps, proj, instance_ids=None, iou_thresh=0.05, fused=True, ordered=False):
+    """Gives every 2-D segment the id of the projected 3-D mask it overlaps best (match_seg.py:111-138).
+
+    seg_maps: ``convert_segments`` maps, int [n, H, W] or [H, W], numpy or tensor (-1 unlabeled, 0 background, > 0 a
+    segment id).  proj: bool [n, k, H, W] (or [k, H, W] with a 2-D map), numpy or tensor - or the int32 words of
+    ``pack_mask_bits`` / ``project_and_match``, which must already be in candidate order.  instance_ids: the id of each
+    candidate, default i + 1.  Per view, every segment id > 0 is scored against each candidate: IoU = |seg & m| /
+    |seg | m| as the fp64 quotient of two integers; the FIRST candidate with the largest IoU gives its id if that IoU
+    exceeds ``iou_thresh`` (in [0, 1]), else the segment becomes -1.  Pixels <= 0 pass through; with k = 0 every segment
+    becomes -1.  Candidates are scored in the reference's order, the string order of ``f"{id}.png"`` (``candidate_order``;
+    it decides ties), unless ``ordered`` says they already come in the order to use.
+
+    -> int32 tensor [n, H, W] ([H, W] for a 2-D map) on the device of the inputs (a GPU tensor among them moves the rest
+    there).  GPU tensors with ``fused=True`` run the HIP kernels of csrc/match.hip (at most 1023 segments per view and
+    1024 candidates); ``fused=False`` or CPU inputs take the composable torch path, bit-identical."""
+    if not 0.0 <= float(iou_thresh) <= 1.0:
+        raise ValueError("iou_thresh must lie in [0, 1]")
+    seg_np = None if torch.is_tensor(seg_maps) else np.asarray(seg_maps)
+    seg = seg_maps if seg_np is None else torch.from_numpy(np.ascontiguousarray(seg_np).astype(np.int32))
+    single = seg.ndim == 2
+    if single:
+        seg = seg[None]
+        seg_np = None if seg_np is None else seg_np[None]
+    if seg.ndim != 3:
+        raise ValueError("seg_maps must be [n, H, W] or [H, W]")
+    n, H, W = (int(v) for v in seg.shape)
+    P = H * W
+    pm = proj if torch.is_tensor(proj) else torch.from_numpy(np.ascontiguousarray(proj))
+    if single and pm.ndim == 3:
+        pm = pm[None]
+    packed = pm.dtype == torch.int32
+    if pm.ndim != 4 or pm.shape[0] != n or tuple(pm.shape[2:]) != (H, W) or not (packed or pm.dtype == torch.bool):
+        raise ValueError(f"proj must be bool [{n}, k, {H}, {W}] or packed int32 words, got {pm.dtype} {tuple(pm.shape)}")
+    if packed and instance_ids is None:
+        raise ValueError("packed words need instance_ids (k is not known otherwise)")
+    ids = list(range(1, pm.shape[1] + 1)) if instance_ids is None else [int(i) for i in np.asarray(
+        instance_ids.cpu() if torch.is_tensor(instance_ids) else instance_ids).reshape(-1)]
+    k = len(ids)
+    if (packed and pm.shape[1] != (k + 31) // 32) or (not packed and pm.shape[1] != k):
+        raise ValueError(f"{k} instance ids for proj of shape {tuple(pm.shape)}")
+    order = list(range(k)) if ordered else candidate_order(ids)
+    if order != list(range(k)):
+        if packed:
+            raise ValueError("packed words must be in candidate order (masks.candidate_order)")
+        pm = pm[:, torch.as_tensor(order, device=pm.device)]
+        ids = [ids[i] for i in order]
+    dev = seg.device if seg.is_cuda else pm.device
+    # ranks: on the host for numpy maps, on the device for tensors
+    if seg_np is not None:
+        ranks, S = _rank_segments_numpy(seg_np.reshape(n, P).astype(np.int32))
+        ranks = torch.from_numpy(ranks).to(dev)
+    else:
+        ranks, S = _rank_segments(seg.to(dev).reshape(n, P).to(torch.int32).contiguous())
+    pm = pm.to(dev)
+    ids_t = torch.tensor(ids, dtype=torch.int32, device=dev)
+    if fused and dev.type == "cuda":
+        if S > MATCH_MAX_SEGMENTS or k > MATCH_MAX_CANDIDATES:
+            raise ValueError(f"the fused match takes at most {MATCH_MAX_SEGMENTS} segments per view and "
+                             f"{MATCH_MAX_CANDIDATES} candidates (got {S}, {k}); use fused=False")
+        words = (pm if packed else pack_mask_bits(pm)).reshape(n, (k + 31) // 32, P).contiguous()
+        out = match_ranked(ranks.contiguous(), words, S, k, ids_t, iou_thresh)
+    else:
+        out = _match_composable(ranks, None if packed else pm, pm.reshape(n, -1, P) if packed else None, S, k, ids_t, iou_thresh)
+    out = out.view(n, H, W)
+    return out[0] if single else out
+
+
+@torch.no_grad()
+def project_and_match(model, masks, bbox_min, bbox_max, poses, intrinsics, H, W, seg_maps, out_dir=None, img_names=None,
+                      thresh=0.5, iou_thresh=0.05):
+    """``project_3d_masks`` and ``match_masks`` in one pass on the device: per view the projector's sums (``soft_project``)
+    are thresholded straight into one bit per candidate (``inr_pack_mask_bits``), and once all views are packed the two
+    match calls run batched over them.  masks [k, W, L, H] (instance id = index + 1), seg_maps ``convert_segments`` maps
+    [n, H, W].  Nothing is copied to the host except, with ``out_dir``, the ``<name>.npy`` int32 files that
+    ``load_matched_masks`` / ``NeRFDataset(mask_dir=...)`` read.  -> int32 tensor [n, H, W] on the model's device."""
+    from . import _lib
+    from ._lib import check, ptr, stream_ptr
+    dev = next(model.parameters()).device
+    poses = torch.as_tensor(poses).to(dev).float()
+    n, k = int(poses.shape[0]), len(masks)
+    if k == 0:
+        raise ValueError("project_and_match: no masks")
+    order = candidate_order(range(1, k + 1))               # pack the candidates in the order the match scores them
+    ids = [i + 1 for i in order]
+    masks = torch.as_tensor(masks)[torch.as_tensor(order)]
+    nw, P = (k + 31) // 32, H * W
+    words = torch.empty(n, nw, H, W, dtype=torch.int32, device=dev)
+    was_training = model.training
+    model.eval()
+    packed = (k, pack_mask_words(masks, dev))
+    lib = _lib.load()
+    for v in range(n):
+        r = get_rays(poses[v:v + 1], intrinsics, H, W, patch=4 if (H % 4 == 0 and W % 4 == 0) else 0)
+        soft, _ = soft_project(model, None, bbox_min, bbox_max, r["rays_o"][0], r["rays_d"][0], packed=packed)
+        inds = r["inds"][0].contiguous()
+        check(lib.inr_pack_mask_bits(ptr(soft, torch.float32, "soft"), ptr(inds, torch.int64, "inds"), int(soft.shape[0]), k,
+                                     float(thresh), P, ptr(words[v]), stream_ptr()), "pack_mask_bits")
+    model.train(was_training)
+    seg = seg_maps if torch.is_tensor(seg_maps) else torch.from_numpy(np.ascontiguousarray(seg_maps).astype(np.int32))
+    out = match_masks(seg.to(dev), words, instance_ids=ids, iou_thresh=iou_thresh, fused=True, ordered=True)
+    if out_dir is not None:
+        os.makedirs(out_dir, exist_ok=True)
+        host = out.cpu().numpy()
+        for v in range(n):
+            np.save(os.path.join(out_dir, f"{img_names[v] if img_names is not None else f'{v:04d}'}.npy"), host[v])
+    return out
+
+
+def match_seg_dir(proj_dir, seg_dir, out_dir, class_names, iou_thresh=0.05, device=None):
+    """Drop-in for the reference script on one scene directory (match_seg.py:94-140): for every ``<img>.npy`` panoptic map
+    with its ``<img>.json`` segment list in ``seg_dir``, takes the projections ``<img>_<id>.png`` of ``proj_dir`` by the
+    reference's rule (``select_projections``, the prefix quirk included; decoded by ``read_png_gray``, foreground > 0),
+    matches, and writes ``<out_dir>/<img>.npy`` (int32).  ``class_names`` as in ``convert_segments``; ``device``: default
+    the GPU when there is one (the HIP kernels), else the composable CPU path.  The ``.hdf5`` mirror and the colour
+    preview the script writes beside each map are NOT written (``load_matched_masks`` reads the ``.npy``).
+    -> list of the image names written."""
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    if isinstance(class_names, (str, os.PathLike)):
+        with open(class_names) as f:
+            class_names = json.load(f)
+    proj_files = os.listdir(proj_dir)
+    os.makedirs(out_dir, exist_ok=True)
+    done = []
+    for f in sorted(x for x in os.listdir(seg_dir) if x.endswith(".npy")):
+        with open(os.path.join(seg_dir, f[:-4] + ".json")) as j:
+            info = json.load(j)
+        seg = convert_segments(np.load(os.path.join(seg_dir, f)), info, class_names)
+        name = f.split(".")[0]
+        files, ids = select_projections(proj_files, name)
+        pm = np.zeros((len(files),) + seg.shape, dtype=bool)
+        for i, pf in enumerate(files):
+            pm[i] = read_png_gray(os.path.join(proj_dir, pf)) > 0
+        out = match_masks(torch.from_numpy(seg).to(device), torch.from_numpy(pm).to(device), instance_ids=ids,
+                          iou_thresh=iou_thresh, ordered=True)
+        np.save(os.path.join(out_dir, f), out.cpu().numpy())
+        done.append(name)
+    return done
