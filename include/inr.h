@@ -672,6 +672,27 @@ int inr_match_assign(const int32_t* seg, const int32_t* seg_area, const int32_t*
                      const int32_t* instance_ids, int64_t B, int64_t P, int32_t S, int32_t k,
                      const double* iou_thresh /*host*/, int32_t* assigned, int32_t* out, inr_stream_t s);
 
+/* ---- 3-D mask overlap (the counts behind the reference's mask_iou_3d, model/utils.py:786-802, which repeats both mask
+ * sets to [N, M, W, L, H]; instance_nerf_amd/evaluate.py turns them into IoU, AP and recall).  Additive: no version
+ * bump.  A mask over V = W * L * H voxels is a BIT PLANE: nW = ceil(V / 64) words, bit v % 64 of word v / 64 = the mask
+ * holds flattened voxel v; the bits of the last word at and above V are zero.  planes uint64 [k, nW].
+ *
+ * inr_pack_mask_planes: masks uint8 (or bool) [k, V], non-zero = inside -> planes [k, nW] and area int32 [k] = voxels
+ *   per mask (zeroed by the call).  One fill and one launch; k = 0 launches nothing (pointers may be null).
+ * inr_pack_label_planes: labels uint8 [V] as extract_instances returns them -> planes [K - first_channel, nW], plane i =
+ *   (label == first_channel + i), and area int32 [K - first_channel].  A label >= K (the 255 of an empty voxel when
+ *   K < 256) lands in no plane.  One fill and one launch; first_channel = K launches nothing.
+ * inr_mask_overlap: inter int32 [kA, kB] = |A_a & B_b| (zeroed by the call) from two plane sets over the same V.
+ *   run_words: words per workgroup, a multiple of 256, or 0 = the library's choice (at least 1024 while the volume has
+ *   them).  One fill and one launch; kA = 0 or kB = 0 launches nothing.
+ * Limits: 1 <= V < 2^31, 0 <= k, kA, kB <= 1024, 1 <= K <= 256, 0 <= first_channel <= K; INR_EINVAL beyond.
+ * Integer atomics only: two calls give identical bits.                                                              */
+int inr_pack_mask_planes(const uint8_t* masks, int32_t k, int64_t V, uint64_t* planes, int32_t* area, inr_stream_t s);
+int inr_pack_label_planes(const uint8_t* labels, int64_t V, int32_t K, int32_t first_channel, uint64_t* planes,
+                          int32_t* area, inr_stream_t s);
+int inr_mask_overlap(const uint64_t* planes_a, int32_t kA, const uint64_t* planes_b, int32_t kB, int64_t V,
+                     int32_t run_words, int32_t* inter, inr_stream_t s);
+
 /* ---- 3-D RoIAlign ("next" row f2; replaces roi_align.roi_align.roi_align_3d, the one FFI call in the
  * reference tree: /root/reference/nerf_rcnn/model/utils.py:604-609).  torchvision roi_align semantics
  * (aligned=False, adaptive ceil(roi/out) sampling grid, average) on three axes: x<->W, y<->L, z<->H.

@@ -128,6 +128,9 @@ _SIGS = {
     "inr_pack_mask_bits": (c_int32, [P, P, c_int64, c_int32, c_float, c_int64, P, P]),
     "inr_match_count": (c_int32, [P, P, c_int64, c_int64, c_int32, c_int32, P, P, P, P, P]),
     "inr_match_assign": (c_int32, [P, P, P, P, P, c_int64, c_int64, c_int32, c_int32, P, P, P, P]),
+    "inr_pack_mask_planes": (c_int32, [P, c_int32, c_int64, P, P, P]),
+    "inr_pack_label_planes": (c_int32, [P, c_int64, c_int32, c_int32, P, P, P]),
+    "inr_mask_overlap": (c_int32, [P, c_int32, P, c_int32, c_int64, c_int32, P, P]),
     "inr_roi_align_3d_set_mode": (c_int32, [c_int32]),
     "inr_roi_align_3d_forward": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32,
                                            c_int32, c_int32, c_float, P, P]),

@@ -1537,6 +1537,20 @@ class Trainer:
         path = os.path.join(save_path, f"{name or self.name}.npz")
         return write_instance_masks_npz(path, extract_instances(self.model, **extract_kwargs), **write_kw)
 
+    def evaluate_instance_masks(self, gt, top_k=None, **extract_kwargs):
+        """Scores the trained instance field's 3-D segmentation against ground truth with the reference's metric
+        (``evaluate.evaluate_masks``: VOC mAP and recall at mask IoU 0.5 and 0.25, and their ``box_`` twins).  ``gt``: a
+        dict in the layout of ``masks.load_3d_masks`` on the extraction's lattice, or the path of such an ``.npz``.
+        ``extract_kwargs`` as for ``save_instance_masks`` (``components=`` and ``labels`` / ``min_voxels`` included): the
+        result equals scoring the file that call writes for the same arguments, without writing it.  Logs the eight
+        numbers.  -> dict."""
+        from ..evaluate import evaluate_masks
+        from ..extract import extract_instances
+        write_kw = {k: extract_kwargs.pop(k) for k in ("labels", "min_voxels") if k in extract_kwargs}
+        out = evaluate_masks(extract_instances(self.model, **extract_kwargs), gt, top_k=top_k, **write_kw)
+        self.log("==> instance masks: " + ", ".join(f"{k} {v:.4f}" for k, v in out.items() if isinstance(v, float)))
+        return out
+
     def _mesh_path(self, save_path):
         return save_path or os.path.join(self.workspace or ".", "meshes", f"{self.name}_{self.epoch}.ply")
 
