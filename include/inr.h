@@ -693,6 +693,46 @@ int inr_pack_label_planes(const uint8_t* labels, int64_t V, int32_t K, int32_t f
 int inr_mask_overlap(const uint64_t* planes_a, int32_t kA, const uint64_t* planes_b, int32_t kB, int64_t V,
                      int32_t run_words, int32_t* inter, inr_stream_t s);
 
+/* ---- Detector tail (what the reference runs between its detector heads and masks/<scene>.npz: per-class 3-D NMS,
+ * model/utils.py:217-267, and paste_masks_in_image, model/utils.py:646-782).  Additive: no version bump.
+ *
+ * inr_paste_masks: probs [N, M, M, M] mask probabilities, boxes [N, 6] = (x1, y1, z1, x2, y2, z2) in grid units (they
+ *   may leave the grid) -> planes uint64 [N, nW] in the bit-plane layout above over V = W * L * H voxels (flattened
+ *   (w, l, h), H fastest; tail bits zero) and area int32 [N] = set bits per mask (zeroed by the call).  Bit = acc >= thresh
+ *   with acc the reference's whole-volume resampling (_do_paste_mask(skip_empty=False): the path its GPU runs take), per
+ *   voxel index (i, j, k), all in fp32, every operation rounded on its own (no fused multiply-add), IEEE division:
+ *     g = (float(i) - x1) / (x2 - x1) * 2 - 1;  p = ((g + 1) / 2) * (M - 1)           (grid_sample, align_corners=True)
+ *   likewise for j with (y1, y2) and k with (z1, z2); p0 = floor(p), p1 = p0 + 1; eight taps added to 0.0f in the order
+ *   (w0,l0,h0) (w0,l0,h1) (w0,l1,h0) (w0,l1,h1) (w1,l0,h0) (w1,l0,h1) (w1,l1,h0) (w1,l1,h1), tap weight = (fh * fl) * fw
+ *   with f = p1 - p on the 0 side and p - p0 on the 1 side, acc = acc + value * weight; a tap with an index outside
+ *   [0, M) on any axis adds nothing (zeros padding).  tests/paste_reference.py is this paragraph in numpy.
+ *   DEPARTURE: a box with a non-finite coordinate or a side <= 0 gives an empty mask (the reference divides by zero; its
+ *   own pipeline drops sides < 1e-2 before this point).
+ *   soft (nullable): fp32 [N, V], acc itself - for tests.  A workgroup (256 words) whose voxels all lie outside the mask's
+ *   support along W - the box widened by one texel (x2 - x1) / (M - 1) on each side - stores zeros without sampling; the
+ *   test evaluates p at the run's first and last w with the arithmetic above, which is monotone in the index, so it
+ *   never drops a set bit.  One fill and one launch; N = 0 launches nothing (pointers may be null).
+ *   Limits: 0 <= N <= 1024, 1 <= M <= 1024, W, L, H >= 1, V < 2^31, thresh >= 0; INR_EINVAL beyond.
+ * inr_planes_to_voxel_words: planes [k, nW] -> words int32 [V] in the layout inr_project_masks_patch reads: bit i of
+ *   words[v] = bit v of plane base + i, i < min(32, k - base); the other bits zero.  1 <= k <= 1024, 0 <= base < k.
+ *   One launch.
+ * inr_nms_3d_pairs: boxes [n, 6] ALREADY SORTED by decreasing score, classes int32 [n] -> pairs uint64 [n, ceil(n / 64)]:
+ *   bit j % 64 of pairs[i][j / 64] = j > i, classes[i] == classes[j] and !(iou(i, j) <= iou_thresh) - the reference's
+ *   survival test `iou <= iou_threshold` (model/utils.py:230) negated, so a NaN IoU suppresses.  IoU = the axis-aligned
+ *   form of model/utils.py:391-462 in fp32 without contraction: volume = ((x2 - x1) * (y2 - y1)) * (z2 - z1), overlap =
+ *   (ex * ey) * ez of the extents min(hi) - max(lo) clamped at 0 (a NaN operand stays NaN), iou = overlap /
+ *   ((volume_i + volume_j) - overlap).  Every word of the matrix is written.  0 <= n <= 4096.  One launch.
+ * inr_nms_3d_scan: the greedy walk over that matrix in ONE workgroup: row i survives unless a surviving row before it
+ *   holds its bit.  keep int32 [n]: the surviving rows in ascending order (= decreasing score) in keep[0 .. n_keep[0]);
+ *   n_keep int32 [1] on the device.  n = 0 writes n_keep = 0 (pairs and keep may be null).  One launch.
+ *   Together the two equal the reference's per-class greedy loop followed by its sort by score, for distinct scores.   */
+int inr_paste_masks(const float* probs, const float* boxes, int32_t N, int32_t M, int32_t W, int32_t L, int32_t H,
+                    float thresh, uint64_t* planes, int32_t* area, float* soft /*nullable*/, inr_stream_t s);
+int inr_planes_to_voxel_words(const uint64_t* planes, int32_t k, int64_t V, int32_t base, int32_t* words, inr_stream_t s);
+int inr_nms_3d_pairs(const float* boxes, const int32_t* classes, int32_t n, float iou_thresh, uint64_t* pairs,
+                     inr_stream_t s);
+int inr_nms_3d_scan(const uint64_t* pairs, int32_t n, int32_t* keep, int32_t* n_keep, inr_stream_t s);
+
 /* ---- 3-D RoIAlign ("next" row f2; replaces roi_align.roi_align.roi_align_3d, the one FFI call in the
  * reference tree: /root/reference/nerf_rcnn/model/utils.py:604-609).  torchvision roi_align semantics
  * (aligned=False, adaptive ceil(roi/out) sampling grid, average) on three axes: x<->W, y<->L, z<->H.

@@ -131,6 +131,10 @@ _SIGS = {
     "inr_pack_mask_planes": (c_int32, [P, c_int32, c_int64, P, P, P]),
     "inr_pack_label_planes": (c_int32, [P, c_int64, c_int32, c_int32, P, P, P]),
     "inr_mask_overlap": (c_int32, [P, c_int32, P, c_int32, c_int64, c_int32, P, P]),
+    "inr_paste_masks": (c_int32, [P, P, c_int32, c_int32, c_int32, c_int32, c_int32, c_float, P, P, P, P]),
+    "inr_planes_to_voxel_words": (c_int32, [P, c_int32, c_int64, c_int32, P, P]),
+    "inr_nms_3d_pairs": (c_int32, [P, P, c_int32, c_float, P, P]),
+    "inr_nms_3d_scan": (c_int32, [P, c_int32, P, P, P]),
     "inr_roi_align_3d_set_mode": (c_int32, [c_int32]),
     "inr_roi_align_3d_forward": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32,
                                            c_int32, c_int32, c_float, P, P]),

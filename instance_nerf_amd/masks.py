@@ -174,16 +174,19 @@ def soft_project(model, masks, bbox_min, bbox_max, rays_o, rays_d, T_thresh=1e-4
 
 @torch.no_grad()
 def project_3d_masks(model, masks, bbox_min, bbox_max, poses, intrinsics, H, W, proj_dir=None, img_names=None,
-                     thresh=0.5):
+                     thresh=0.5, packed=None):
     """-> bool array [n_views, k, H, W]; when ``proj_dir`` is given also writes ``<img>_<inst>.png``
-    (inst = mask index + 1) for every non-empty projection."""
+    (inst = mask index + 1) for every non-empty projection.  ``packed``: ``(k, words)`` with the words of
+    ``pack_mask_words`` - or of ``detections.planes_to_voxel_words`` for masks that exist as bit planes - handed to
+    ``soft_project`` in place of ``masks`` (which may then be None)."""
     dev = next(model.parameters()).device
     poses = torch.as_tensor(poses).to(dev).float()
-    k = len(masks)
+    k = len(masks) if packed is None else int(packed[0])
     out = np.zeros((poses.shape[0], k, H, W), dtype=bool)
     was_training = model.training
     model.eval()
-    packed = (k, pack_mask_words(masks, dev))          # one 32-bit word per voxel and 32 masks, built once for all views
+    if packed is None:
+        packed = (k, pack_mask_words(masks, dev))      # one 32-bit word per voxel and 32 masks, built once for all views
     for v in range(poses.shape[0]):
         r = get_rays(poses[v:v + 1], intrinsics, H, W, patch=4 if (H % 4 == 0 and W % 4 == 0) else 0)
         soft, _ = soft_project(model, None, bbox_min, bbox_max, r["rays_o"][0], r["rays_d"][0], packed=packed)
@@ -482,27 +485,30 @@ def match_masks(seg_maps, proj, instance_ids=None, iou_thresh=0.05, fused=True, 
 
 @torch.no_grad()
 def project_and_match(model, masks, bbox_min, bbox_max, poses, intrinsics, H, W, seg_maps, out_dir=None, img_names=None,
-                      thresh=0.5, iou_thresh=0.05):
+                      thresh=0.5, iou_thresh=0.05, packed=None):
     """``project_3d_masks`` and ``match_masks`` in one pass on the device: per view the projector's sums (``soft_project``)
     are thresholded straight into one bit per candidate (``inr_pack_mask_bits``), and once all views are packed the two
     match calls run batched over them.  masks [k, W, L, H] (instance id = index + 1), seg_maps ``convert_segments`` maps
     [n, H, W].  Nothing is copied to the host except, with ``out_dir``, the ``<name>.npy`` int32 files that
-    ``load_matched_masks`` / ``NeRFDataset(mask_dir=...)`` read.  -> int32 tensor [n, H, W] on the model's device."""
+    ``load_matched_masks`` / ``NeRFDataset(mask_dir=...)`` read.  -> int32 tensor [n, H, W] on the model's device.
+    ``packed``: ``(k, words)`` handed to ``soft_project`` in place of ``masks`` (which may then be None); the words must
+    hold the masks in CANDIDATE ORDER (``candidate_order(range(1, k + 1))``, the ``order`` argument of
+    ``detections.planes_to_voxel_words``)."""
     from . import _lib
     from ._lib import check, ptr, stream_ptr
     dev = next(model.parameters()).device
     poses = torch.as_tensor(poses).to(dev).float()
-    n, k = int(poses.shape[0]), len(masks)
+    n, k = int(poses.shape[0]), len(masks) if packed is None else int(packed[0])
     if k == 0:
         raise ValueError("project_and_match: no masks")
     order = candidate_order(range(1, k + 1))               # pack the candidates in the order the match scores them
     ids = [i + 1 for i in order]
-    masks = torch.as_tensor(masks)[torch.as_tensor(order)]
     nw, P = (k + 31) // 32, H * W
     words = torch.empty(n, nw, H, W, dtype=torch.int32, device=dev)
     was_training = model.training
     model.eval()
-    packed = (k, pack_mask_words(masks, dev))
+    if packed is None:
+        packed = (k, pack_mask_words(torch.as_tensor(masks)[torch.as_tensor(order)], dev))
     lib = _lib.load()
     for v in range(n):
         r = get_rays(poses[v:v + 1], intrinsics, H, W, patch=4 if (H % 4 == 0 and W % 4 == 0) else 0)
