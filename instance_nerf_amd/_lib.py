@@ -222,6 +222,12 @@ def ptr(t, dtype=None, name="tensor", allow_none=False):
     return c_void_p(t.data_ptr())
 
 
+def ptr_or_null(t, dtype=None, name="tensor"):
+    """``ptr`` for an argument the library takes as null when it holds no element: None or an empty tensor gives a null
+    pointer (unchecked), anything else goes through ``ptr``."""
+    return None if t is None or t.numel() == 0 else ptr(t, dtype, name)
+
+
 def host_ptr(t, dtype, name="tensor"):
     if t.is_cuda or not t.is_contiguous() or t.dtype != dtype:
         raise RuntimeError(f"{name} must be a contiguous CPU {dtype} tensor")

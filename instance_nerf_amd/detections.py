@@ -5,7 +5,7 @@ model/nerf_rcnn.py:606-635) and ``paste_masks_in_image`` (model/utils.py:646-782
 which resamples each M^3 mask probability into the scene grid and thresholds it at 0.5, and writes the top detections
 with ``np.savez`` (run_rcnn.py:652-666).  On a GPU its paste samples the whole volume per mask through an
 [N, W, L, H, 3] fp32 grid to produce one bit per voxel; here the bits are produced directly (csrc/detect.hip), in the
-bit-plane layout ``evaluate.pack_mask_planes`` defines, which the mask metric and - through
+bit-plane layout of maskbits.py, which the mask metric and - through
 ``planes_to_voxel_words`` - the projector take as they are.
 
 * ``nms_3d`` / ``batched_nms_3d``: indices of the surviving boxes in decreasing score order.
@@ -30,7 +30,9 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from .evaluate import _as_tensor, _pack_bits_torch, _unpack_bits_torch, _words, box_iou_3d
+from . import _lib
+from .evaluate import box_iou_3d
+from .maskbits import as_tensor, interleave32, pack_planes, unpack_planes, words
 
 NMS_MAX_BOXES = 4096            # include/inr.h: limit of inr_nms_3d_pairs / inr_nms_3d_scan
 PASTE_MAX_MASKS, PASTE_MAX_M = 1024, 1024        # include/inr.h: limits of inr_paste_masks
@@ -39,7 +41,7 @@ _PASTE_CHUNK_BYTES = 1 << 28    # fp32 bytes of one grid_sample output of the co
 
 # ---- NMS -----------------------------------------------------------------------------------------------------------------
 def _check_boxes(boxes, who):
-    b = _as_tensor(boxes)
+    b = as_tensor(boxes)
     if b.ndim != 2 or b.shape[1] != 6:
         raise ValueError(f"{who}: boxes must be [n, 6] (x1, y1, z1, x2, y2, z2); oriented boxes are not supported")
     return b.float()
@@ -71,7 +73,7 @@ def batched_nms_3d(boxes, scores, idxs, iou_threshold, fused=True):
     back but the number of survivors.  The kernels compare class ids as int32: an id outside that range raises
     ValueError (after the launches, with the same read-back).  Above 4096 boxes, on the CPU, or with ``fused=False``: the greedy torch loop."""
     b = _check_boxes(boxes, "batched_nms_3d")
-    sc, cl = _as_tensor(scores).to(b.device).reshape(-1), _as_tensor(idxs).to(b.device).reshape(-1)
+    sc, cl = as_tensor(scores).to(b.device).reshape(-1), as_tensor(idxs).to(b.device).reshape(-1)
     n = int(b.shape[0])
     if sc.shape[0] != n or cl.shape[0] != n:
         raise ValueError(f"batched_nms_3d: {n} boxes, {sc.shape[0]} scores, {cl.shape[0]} classes")
@@ -81,21 +83,19 @@ def batched_nms_3d(boxes, scores, idxs, iou_threshold, fused=True):
     bs, cs = b[order].contiguous(), cl[order]
     if not (b.is_cuda and fused and n <= NMS_MAX_BOXES):
         return order[_greedy_sorted(bs, cs, float(iou_threshold))]
-    from . import _lib
     lib = _lib.load()
     keep = torch.empty(n, dtype=torch.int32, device=b.device)
     n_keep = torch.empty(1, dtype=torch.int32, device=b.device)
     wide = torch.zeros(1, dtype=torch.int32, device=b.device)
-    none = n == 0
-    if not none:
+    pairs = None
+    if n > 0:
         if cs.dtype == torch.int64:     # the kernels compare int32 ids: checked, never wrapped
             wide = ((cs < -2 ** 31) | (cs > 2 ** 31 - 1)).any().to(torch.int32).view(1)
         cs = cs.to(torch.int32).contiguous()
         pairs = torch.empty(n, (n + 63) // 64, dtype=torch.int64, device=b.device)
         _lib.check(lib.inr_nms_3d_pairs(_lib.ptr(bs, torch.float32, "boxes"), _lib.ptr(cs, torch.int32, "classes"), n,
                                         float(iou_threshold), _lib.ptr(pairs), _lib.stream_ptr()), "nms_3d_pairs")
-    _lib.check(lib.inr_nms_3d_scan(_lib.ptr(None if none else pairs, allow_none=none), n,
-                                   _lib.ptr(None if none else keep, allow_none=none), _lib.ptr(n_keep), _lib.stream_ptr()),
+    _lib.check(lib.inr_nms_3d_scan(_lib.ptr_or_null(pairs), n, _lib.ptr_or_null(keep), _lib.ptr(n_keep), _lib.stream_ptr()),
                "nms_3d_scan")
     kept, bad = torch.cat([n_keep, wide]).tolist()                 # the one read-back
     if bad:
@@ -116,7 +116,7 @@ def postprocess_detections(boxes, scores, image_shape, score_thresh=0.01, nms_th
     class 0 = background).  Clip every box to the grid ``image_shape`` = (W, L, H); drop class 0; make every (proposal,
     class) pair a detection; keep ``score > score_thresh``; drop boxes with a side < 1e-2; per-class NMS at
     ``nms_thresh``; the first ``detections_per_img`` by score.  -> ``(boxes [k, 6], scores [k], labels int64 [k])``."""
-    b, sc = _as_tensor(boxes).float(), _as_tensor(scores)
+    b, sc = as_tensor(boxes).float(), as_tensor(scores)
     if b.ndim != 3 or b.shape[2] != 6 or sc.ndim != 2 or tuple(sc.shape) != tuple(b.shape[:2]):
         raise ValueError(f"postprocess_detections: boxes must be [n, C, 6] and scores [n, C], got {tuple(b.shape)}, {tuple(sc.shape)}")
     sc = sc.to(b.device)
@@ -135,10 +135,10 @@ def postprocess_detections(boxes, scores, image_shape, score_thresh=0.01, nms_th
 
 # ---- paste ---------------------------------------------------------------------------------------------------------------
 def _check_paste(mask_probs, boxes, image_shape, threshold, who):
-    m = _as_tensor(mask_probs)
+    m = as_tensor(mask_probs)
     if m.ndim != 4 or not (m.shape[1] == m.shape[2] == m.shape[3]) or m.shape[1] < 1:
         raise ValueError(f"{who}: mask_probs must be [N, M, M, M] (only cube mask predictions are supported), got {tuple(m.shape)}")
-    b = _as_tensor(boxes)
+    b = as_tensor(boxes)
     if b.ndim != 2 or b.shape[1] != 6 or b.shape[0] != m.shape[0]:
         raise ValueError(f"{who}: boxes must be [{m.shape[0]}, 6], got {tuple(b.shape)}")
     shape = tuple(int(v) for v in image_shape)
@@ -202,29 +202,22 @@ def paste_masks(mask_probs, boxes, image_shape, threshold=0.5, out="planes", fus
         if out == "masks":
             return bits
         flat = bits.reshape(N, V)
-        return _pack_bits_torch(flat.to(torch.uint8)), flat.sum(1).to(torch.int32), shape
-    from . import _lib
+        return pack_planes(flat), flat.sum(1).to(torch.int32), shape
     if N > PASTE_MAX_MASKS or M > PASTE_MAX_M:
         raise ValueError(f"the fused paste takes at most {PASTE_MAX_MASKS} masks of resolution at most {PASTE_MAX_M} "
                          f"(got {N}, {M}); use fused=False")
-    planes = torch.empty(N, _words(V), dtype=torch.int64, device=m.device)
+    planes = torch.empty(N, words(V), dtype=torch.int64, device=m.device)
     area = torch.empty(N, dtype=torch.int32, device=m.device)
     soft = torch.empty((N,) + shape, dtype=torch.float32, device=m.device) if out == "soft" else None
-    none = N == 0
-    _lib.check(_lib.load().inr_paste_masks(_lib.ptr(None if none else m, torch.float32, "mask_probs", allow_none=none),
-                                           _lib.ptr(None if none else b, torch.float32, "boxes", allow_none=none),
-                                           N, M, shape[0], shape[1], shape[2], float(threshold),
-                                           _lib.ptr(None if none else planes, allow_none=none),
-                                           _lib.ptr(None if none else area, allow_none=none),
-                                           _lib.ptr(None if none or soft is None else soft, allow_none=True),
+    P = _lib.ptr_or_null
+    _lib.check(_lib.load().inr_paste_masks(P(m, torch.float32, "mask_probs"), P(b, torch.float32, "boxes"), N, M, shape[0],
+                                           shape[1], shape[2], float(threshold), P(planes), P(area), P(soft),
                                            _lib.stream_ptr()), "paste_masks")
     if out == "soft":
         return soft
     if out == "planes":
         return planes, area, shape
-    if N == 0:
-        return torch.zeros((0,) + shape, dtype=torch.bool, device=m.device)
-    return _unpack_bits_torch(planes, V).bool().view((N,) + shape)
+    return unpack_planes(planes, V).bool().view((N,) + shape)
 
 
 # ---- bit planes -> the projector's words ---------------------------------------------------------------------------------
@@ -238,20 +231,14 @@ def planes_to_voxel_words(packed, order=None, fused=True):
     planes, _, shape = packed
     shape = tuple(int(v) for v in shape)
     k, V = int(planes.shape[0]), int(np.prod(shape))
-    if planes.dtype != torch.int64 or planes.ndim != 2 or planes.shape[1] != _words(V):
-        raise ValueError(f"planes must be int64 [k, {_words(V)}] for the volume {shape}")
+    if planes.dtype != torch.int64 or planes.ndim != 2 or planes.shape[1] != words(V):
+        raise ValueError(f"planes must be int64 [k, {words(V)}] for the volume {shape}")
     if order is not None:
         planes = planes[torch.as_tensor(list(order), dtype=torch.int64, device=planes.device)]
     planes = planes.contiguous()
-    out = []
     if not (planes.is_cuda and fused):
-        for base in range(0, k, 32):
-            bits = _unpack_bits_torch(planes[base:base + 32], V).to(torch.int64)
-            w = (bits << torch.arange(bits.shape[0], device=planes.device, dtype=torch.int64).view(-1, 1)).sum(0)
-            w = torch.where(w >= 2 ** 31, w - 2 ** 32, w)
-            out.append(w.to(torch.int32).view(shape).contiguous())
-        return out
-    from . import _lib
+        return [interleave32(unpack_planes(planes[base:base + 32], V).bool()).view(shape) for base in range(0, k, 32)]
+    out = []
     lib = _lib.load()
     for base in range(0, k, 32):
         w = torch.empty(shape, dtype=torch.int32, device=planes.device)
@@ -270,18 +257,17 @@ def write_detections_npz(path, mask_probs, boxes, scores, labels, image_shape, t
     planes, the planes copied to the host and unpacked there.  Keys: ``masks`` bool [k, W, L, H], ``scores`` float32 [k]
     descending, ``labels`` int64 [k], ``boxes`` float32 [k, 6] - what ``masks.load_3d_masks`` reads.  A scene without
     detections (or ``top_k=0``) writes the same keys with k = 0, as the reference does.  -> path."""
-    sc = _as_tensor(scores).detach().reshape(-1)
+    sc = as_tensor(scores).detach().reshape(-1)
     n = int(sc.shape[0])
-    m, b = _as_tensor(mask_probs), _as_tensor(boxes)
-    lab = _as_tensor(labels).detach().reshape(-1)
+    m, b = as_tensor(mask_probs), as_tensor(boxes)
+    lab = as_tensor(labels).detach().reshape(-1)
     if m.shape[0] != n or b.shape[0] != n or lab.shape[0] != n:
         raise ValueError(f"write_detections_npz: {n} scores, {m.shape[0]} masks, {b.shape[0]} boxes, {lab.shape[0]} labels")
     inds = torch.sort(sc, descending=True, stable=True).indices[:max(int(top_k), 0)]
     m, b = m[inds.to(m.device)], b[inds.to(b.device)]
     planes, _, shape = paste_masks(m, b, image_shape, threshold, out="planes", fused=fused)
     k, V = int(planes.shape[0]), int(np.prod(shape))
-    words = planes.cpu().numpy().view(np.uint64)
-    bits = np.unpackbits(words.view(np.uint8).reshape(k, words.shape[1] * 8), axis=1, bitorder="little")[:, :V]
+    bits = unpack_planes(planes.cpu(), V).numpy()
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     np.savez_compressed(path, masks=bits.astype(bool).reshape((k,) + shape), scores=sc[inds].cpu().numpy().astype(np.float32),
                         labels=lab[inds.to(lab.device)].cpu().numpy().astype(np.int64),

@@ -22,13 +22,13 @@ import os
 import numpy as np
 import torch
 
+from . import _lib
+from .maskbits import as_tensor, pack_planes, unpack_planes, words
+from .masks import instance_detections, load_3d_masks
+
 OVERLAP_MAX_MASKS, OVERLAP_MAX_CHANNELS = 1024, 256        # include/inr.h: limits of the overlap exports
 OVERLAP_MIN_RUN_WORDS = 1024        # csrc/overlap.hip kMinRun: fewest words per workgroup of the default pair-count launch
 _CHUNK = 1 << 20                    # voxels per matmul of the composable path (counts of a chunk are exact in fp32)
-
-
-def _as_tensor(x):
-    return x if torch.is_tensor(x) else torch.from_numpy(np.ascontiguousarray(x))
 
 
 def _is_packed(m):
@@ -37,7 +37,7 @@ def _is_packed(m):
 
 def _flat_masks(masks, who):
     """bool / uint8 [k, W, L, H] (numpy or tensor) -> (uint8 view [k, V], (W, L, H))."""
-    m = _as_tensor(masks)
+    m = as_tensor(masks)
     if m.ndim != 4 or m.dtype not in (torch.bool, torch.uint8):
         raise ValueError(f"{who}: masks must be bool or uint8 [k, W, L, H], got {m.dtype} {tuple(m.shape)}")
     shape = tuple(int(v) for v in m.shape[1:])
@@ -48,7 +48,7 @@ def _flat_masks(masks, who):
 
 
 def _check_labels(labels, K, first_channel, who):
-    lab = _as_tensor(labels)
+    lab = as_tensor(labels)
     if lab.ndim != 3 or lab.dtype != torch.uint8 or lab.numel() == 0:
         raise ValueError(f"{who}: labels must be a non-empty uint8 [W, L, H] volume, got {lab.dtype} {tuple(lab.shape)}")
     if not 1 <= int(K) <= OVERLAP_MAX_CHANNELS or not 0 <= int(first_channel) <= int(K):
@@ -56,28 +56,7 @@ def _check_labels(labels, K, first_channel, who):
     return lab.contiguous(), tuple(int(v) for v in lab.shape)
 
 
-def _words(V):
-    return (V + 63) // 64
-
-
-# ---- bit planes --------------------------------------------------------------------------------------------------------
-def _pack_bits_torch(flat):
-    """uint8 [k, V] -> int64 planes [k, ceil(V / 64)] in plain torch (the layout of include/inr.h)."""
-    k, V = flat.shape
-    nW = _words(V)
-    bits = torch.zeros(k, nW * 64, dtype=torch.int64, device=flat.device)
-    bits[:, :V] = (flat != 0).to(torch.int64)
-    shifts = torch.arange(64, device=flat.device, dtype=torch.int64)
-    return (bits.view(k, nW, 64) << shifts).sum(-1)        # bit 63 wraps to the sign: the same 64 bits
-
-
-def _unpack_bits_torch(planes, V):
-    """int64 planes [k, nW] -> uint8 [k, V]."""
-    shifts = torch.arange(64, device=planes.device, dtype=torch.int64)
-    bits = (planes.unsqueeze(-1) >> shifts) & 1
-    return bits.reshape(planes.shape[0], -1)[:, :V].to(torch.uint8)
-
-
+# ---- bit planes (the layout: maskbits.py) ------------------------------------------------------------------------------
 def pack_mask_planes(masks, device=None, fused=True):
     """bool / uint8 [k, W, L, H] masks (non-zero = inside) -> ``(planes int64 [k, ceil(V / 64)], area int32 [k], (W, L, H))``
     on ``device`` (default: where the masks live): bit v % 64 of word v / 64 of row i = mask i holds flattened voxel v,
@@ -89,17 +68,13 @@ def pack_mask_planes(masks, device=None, fused=True):
         flat = flat.to(device)
     k, V = (int(v) for v in flat.shape)
     if not (flat.is_cuda and fused):
-        return _pack_bits_torch(flat), (flat != 0).sum(1).to(torch.int32), shape
-    from . import _lib
+        return pack_planes(flat), (flat != 0).sum(1).to(torch.int32), shape
     if k > OVERLAP_MAX_MASKS:
         raise ValueError(f"the fused pack takes at most {OVERLAP_MAX_MASKS} masks (got {k}); use fused=False")
-    planes = torch.empty(k, _words(V), dtype=torch.int64, device=flat.device)
+    planes = torch.empty(k, words(V), dtype=torch.int64, device=flat.device)
     area = torch.empty(k, dtype=torch.int32, device=flat.device)
-    none = k == 0
-    _lib.check(_lib.load().inr_pack_mask_planes(_lib.ptr(None if none else flat, torch.uint8, "masks", allow_none=none), k, V,
-                                                _lib.ptr(None if none else planes, allow_none=none),
-                                                _lib.ptr(None if none else area, allow_none=none), _lib.stream_ptr()),
-               "pack_mask_planes")
+    _lib.check(_lib.load().inr_pack_mask_planes(_lib.ptr_or_null(flat, torch.uint8, "masks"), k, V, _lib.ptr_or_null(planes),
+                                                _lib.ptr_or_null(area), _lib.stream_ptr()), "pack_mask_planes")
     return planes, area, shape
 
 
@@ -115,22 +90,17 @@ def pack_label_planes(labels, K, first_channel=1, device=None, fused=True):
     k, V = K - first, lab.numel()
     if not (lab.is_cuda and fused):
         onehot = lab.reshape(1, V) == torch.arange(first, K, device=lab.device, dtype=torch.int64).view(k, 1)
-        return _pack_bits_torch(onehot.to(torch.uint8)), onehot.sum(1).to(torch.int32), shape
-    from . import _lib
-    planes = torch.empty(k, _words(V), dtype=torch.int64, device=lab.device)
+        return pack_planes(onehot), onehot.sum(1).to(torch.int32), shape
+    planes = torch.empty(k, words(V), dtype=torch.int64, device=lab.device)
     area = torch.empty(k, dtype=torch.int32, device=lab.device)
-    none = k == 0
-    _lib.check(_lib.load().inr_pack_label_planes(_lib.ptr(lab, torch.uint8, "labels"), V, K, first,
-                                                 _lib.ptr(None if none else planes, allow_none=none),
-                                                 _lib.ptr(None if none else area, allow_none=none), _lib.stream_ptr()),
-               "pack_label_planes")
+    _lib.check(_lib.load().inr_pack_label_planes(_lib.ptr(lab, torch.uint8, "labels"), V, K, first, _lib.ptr_or_null(planes),
+                                                 _lib.ptr_or_null(area), _lib.stream_ptr()), "pack_label_planes")
     return planes, area, shape
 
 
 def overlap_planes(packed1, packed2, run_words=0):
     """The pair-count launch on two packed mask sets over the same volume -> inter int32 [k1, k2] (``inr_mask_overlap``).
     ``run_words``: words per workgroup, a multiple of 256; 0 = the library's choice."""
-    from . import _lib
     (p1, _, s1), (p2, _, s2) = packed1, packed2
     if tuple(s1) != tuple(s2):
         raise ValueError(f"the two mask sets cover different volumes: {tuple(s1)} and {tuple(s2)}")
@@ -146,86 +116,76 @@ def overlap_planes(packed1, packed2, run_words=0):
 
 
 # ---- counts ------------------------------------------------------------------------------------------------------------
-def _chunk_rows(src, lo, hi):
-    """Rows of one operand over voxels [lo, hi) as a float matrix: src is ("flat", uint8 [k, V]) or ("labels", uint8 [V],
-    first, K)."""
-    dtype = torch.float32 if src[1].is_cuda else torch.float64
-    if src[0] == "flat":
-        return (src[1][:, lo:hi] != 0).to(dtype)
-    _, lab, first, K = src
-    ch = torch.arange(first, K, device=lab.device, dtype=torch.int64).view(-1, 1)
-    return (lab[lo:hi].view(1, -1) == ch).to(dtype)
+class _Operand:
+    """One side of ``_overlap``: k masks over a volume ``shape``, held as exactly one of flat uint8 masks [k, V], the
+    (planes, area) of a packed triple, or a flattened label volume uint8 [V] whose channels first..K-1 are the masks."""
+
+    def __init__(self, shape, flat=None, packed=None, labels=None, first=0, K=0):
+        self.shape, self.V = tuple(int(v) for v in shape), int(np.prod(shape))
+        self.flat, self.packed, self.labels, self.first, self.K = flat, packed, labels, first, K
+        held = labels if labels is not None else flat if flat is not None else packed[0]
+        self.device, self.k = held.device, K - first if labels is not None else int(held.shape[0])
+
+    @classmethod
+    def of_masks(cls, m, who):
+        """bool / uint8 [k, W, L, H] masks, or - the second constructor - the triple of ``pack_mask_planes``."""
+        if _is_packed(m):
+            return cls(m[2], packed=(m[0], m[1]))
+        flat, shape = _flat_masks(m, who)
+        return cls(shape, flat=flat)
+
+    @classmethod
+    def of_labels(cls, labels, K, first_channel, who):
+        lab, shape = _check_labels(labels, K, first_channel, who)
+        return cls(shape, labels=lab.reshape(-1), first=int(first_channel), K=int(K))
+
+    def to(self, dev):
+        def move(t):
+            return None if t is None else t.to(dev)
+        return _Operand(self.shape, move(self.flat), None if self.packed is None else tuple(move(t) for t in self.packed),
+                        move(self.labels), self.first, self.K)
+
+    def planes(self):
+        """The fused route: ``(planes, area, shape)``, packed by the kernels unless the operand came packed."""
+        if self.packed is not None:
+            return self.packed[0].contiguous(), self.packed[1], self.shape
+        if self.flat is not None:
+            return pack_mask_planes(self.flat.view((self.k,) + self.shape))
+        return pack_label_planes(self.labels.view(self.shape), self.K, self.first)
+
+    def rows(self, lo, hi):
+        """The composable route: the masks over voxels [lo, hi), lo a multiple of 64, as a 0 / 1 float matrix [k, hi - lo]
+        (fp32 on the GPU, fp64 on the CPU)."""
+        dtype = torch.float32 if self.device.type == "cuda" else torch.float64
+        if self.labels is not None:
+            ch = torch.arange(self.first, self.K, device=self.device, dtype=torch.int64).view(-1, 1)
+            return (self.labels[lo:hi].view(1, -1) == ch).to(dtype)
+        if self.flat is not None:
+            return (self.flat[:, lo:hi] != 0).to(dtype)
+        return unpack_planes(self.packed[0][:, lo // 64:words(hi)], hi - lo).to(dtype)
 
 
-def _counts_composable(src1, src2, V):
-    """inter int64 [k1, k2], area1 int64 [k1], area2 int64 [k2] as chunked matmuls of 0/1 matrices: a chunk holds at most
-    2^20 voxels, so every entry of a product is an integer below 2^24 and exact in fp32 (GPU) or fp64 (CPU)."""
-    def rows(src):
-        return src[1].shape[0] if src[0] == "flat" else src[3] - src[2]
-    dev = src1[1].device
-    k1, k2 = rows(src1), rows(src2)
-    inter = torch.zeros(k1, k2, dtype=torch.int64, device=dev)
-    a1 = torch.zeros(k1, dtype=torch.int64, device=dev)
-    a2 = torch.zeros(k2, dtype=torch.int64, device=dev)
-    for lo in range(0, V, _CHUNK):
-        hi = min(V, lo + _CHUNK)
-        x, y = _chunk_rows(src1, lo, hi), _chunk_rows(src2, lo, hi)
+def _overlap(op1, op2, fused, who):
+    """-> (inter int64 [k1, k2], area1 int64 [k1], area2 int64 [k2]) of two ``_Operand``s, on the GPU if either lives
+    there.  Fused: two packs (unless packed already) and the pair-count launch.  Composable: chunked matmuls of 0 / 1
+    matrices; a chunk holds at most 2^20 voxels, so every entry of a product is an integer below 2^24 and exact in fp32
+    (GPU) or fp64 (CPU)."""
+    if op1.shape != op2.shape:
+        raise ValueError(f"{who}: the two mask sets cover different volumes: {op1.shape} and {op2.shape}")
+    dev = op2.device if op2.device.type == "cuda" and op1.device.type != "cuda" else op1.device
+    op1, op2 = op1.to(dev), op2.to(dev)
+    if fused and dev.type == "cuda":
+        pa, pb = op1.planes(), op2.planes()
+        return overlap_planes(pa, pb).long(), pa[1].long(), pb[1].long()
+    inter = torch.zeros(op1.k, op2.k, dtype=torch.int64, device=dev)
+    a1 = torch.zeros(op1.k, dtype=torch.int64, device=dev)
+    a2 = torch.zeros(op2.k, dtype=torch.int64, device=dev)
+    for lo in range(0, op1.V, _CHUNK):
+        x, y = op1.rows(lo, min(op1.V, lo + _CHUNK)), op2.rows(lo, min(op1.V, lo + _CHUNK))
         inter += (x @ y.t()).to(torch.int64)
         a1 += x.sum(1).to(torch.int64)
         a2 += y.sum(1).to(torch.int64)
     return inter, a1, a2
-
-
-def _operand(m, who):
-    """masks or a packed triple -> ("flat" | "packed", tensor(s), shape)."""
-    if _is_packed(m):
-        return "packed", (m[0], m[1]), tuple(int(v) for v in m[2])
-    flat, shape = _flat_masks(m, who)
-    return "flat", flat, shape
-
-
-def _pick_device(*tensors):
-    for t in tensors:
-        if t.is_cuda:
-            return t.device
-    return tensors[0].device
-
-
-def _overlap(op1, op2, fused, who):
-    """op = ("flat", uint8 [k, V], shape) | ("packed", (planes, area), shape) | ("labels", (uint8 [V], first, K), shape)."""
-    if op1[2] != op2[2]:
-        raise ValueError(f"{who}: the two mask sets cover different volumes: {op1[2]} and {op2[2]}")
-    shape, V = op1[2], int(np.prod(op1[2]))
-
-    def first_tensor(op):
-        return op[1][0] if isinstance(op[1], tuple) else op[1]
-    dev = _pick_device(first_tensor(op1), first_tensor(op2))
-
-    def move(op):
-        kind, data, _ = op
-        if kind == "flat":
-            return kind, data.to(dev)
-        if kind == "packed":
-            return kind, (data[0].to(dev), data[1].to(dev))
-        return kind, (data[0].to(dev), data[1], data[2])
-    (k1, d1), (k2, d2) = move(op1), move(op2)
-    if fused and dev.type == "cuda":
-        def packed(kind, d):
-            if kind == "packed":
-                return d[0].contiguous(), d[1], shape
-            if kind == "flat":
-                return pack_mask_planes(d.view((d.shape[0],) + shape))
-            return pack_label_planes(d[0].view(shape), d[2], d[1])
-        pa, pb = packed(k1, d1), packed(k2, d2)
-        return overlap_planes(pa, pb).long(), pa[1].long(), pb[1].long()
-
-    def source(kind, d):
-        if kind == "flat":
-            return "flat", d
-        if kind == "packed":
-            return "flat", _unpack_bits_torch(d[0], V)
-        return "labels", d[0], d[1], d[2]
-    return _counts_composable(source(k1, d1), source(k2, d2), V)
 
 
 def iou_from_counts(inter, area1, area2):
@@ -241,7 +201,7 @@ def iou_from_counts(inter, area1, area2):
 def mask_overlap(masks1, masks2, fused=True):
     """-> ``(inter int64 [N, M], area1 int64 [N], area2 int64 [M])``: voxels shared by every pair and voxels per mask.
     Inputs as ``mask_iou_3d``."""
-    return _overlap(_operand(masks1, "mask_overlap"), _operand(masks2, "mask_overlap"), fused, "mask_overlap")
+    return _overlap(_Operand.of_masks(masks1, "mask_overlap"), _Operand.of_masks(masks2, "mask_overlap"), fused, "mask_overlap")
 
 
 @torch.no_grad()
@@ -256,9 +216,8 @@ def mask_iou_3d(masks1, masks2, fused=True):
 @torch.no_grad()
 def label_mask_overlap(labels, K, masks2, first_channel=1, fused=True):
     """As ``mask_overlap`` with the first set given as a label volume: row i is the mask ``labels == first_channel + i``."""
-    lab, shape = _check_labels(labels, K, first_channel, "label_mask_overlap")
-    return _overlap(("labels", (lab.reshape(-1), int(first_channel), int(K)), shape),
-                    _operand(masks2, "label_mask_overlap"), fused, "label_mask_overlap")
+    return _overlap(_Operand.of_labels(labels, K, first_channel, "label_mask_overlap"),
+                    _Operand.of_masks(masks2, "label_mask_overlap"), fused, "label_mask_overlap")
 
 
 @torch.no_grad()
@@ -272,7 +231,7 @@ def box_iou_3d(boxes1, boxes2):
     """Pairwise IoU of axis-aligned boxes (x1, y1, z1, x2, y2, z2) -> [N, M], the reference's AABB form
     (model/utils.py:391-462): volumes and the clamped overlap extents multiplied axis by axis in the boxes' own float
     type, union = volume1 + volume2 - overlap.  Plain torch on the inputs' device."""
-    b1, b2 = _as_tensor(boxes1), _as_tensor(boxes2)
+    b1, b2 = as_tensor(boxes1), as_tensor(boxes2)
     if b1.ndim != 2 or b2.ndim != 2 or b1.shape[1] != 6 or b2.shape[1] != 6:
         raise ValueError("box_iou_3d: boxes must be [N, 6] and [M, 6] (oriented boxes are not supported)")
     if not b1.is_floating_point():
@@ -324,11 +283,11 @@ def evaluate_map_recall(pred_list, scores_list, labels_list, gt_list, gt_labels_
         raise ValueError("iou_type must be 'box' or 'mask'")
     n_gt, scores, flags = {}, {}, {}
     for s in range(len(scores_list)):
-        sc = _as_tensor(scores_list[s]).detach().cpu().reshape(-1)
-        pl = _as_tensor(labels_list[s]).detach().cpu().reshape(-1).to(torch.int64)
-        gl = _as_tensor(gt_labels_list[s]).detach().cpu().reshape(-1).to(torch.int64)
+        sc = as_tensor(scores_list[s]).detach().cpu().reshape(-1)
+        pl = as_tensor(labels_list[s]).detach().cpu().reshape(-1).to(torch.int64)
+        gl = as_tensor(gt_labels_list[s]).detach().cpu().reshape(-1).to(torch.int64)
         if iou_list is not None:
-            iou = _as_tensor(iou_list[s])
+            iou = as_tensor(iou_list[s])
         elif len(pl) == 0 or len(gl) == 0:
             iou = torch.zeros(len(pl), len(gl))
         elif iou_type == "mask":
@@ -386,7 +345,6 @@ def _is_extract_result(d):
 
 def _load_scene(d, who):
     if isinstance(d, (str, os.PathLike)):
-        from .masks import load_3d_masks
         d = load_3d_masks(d)
     missing = {"masks", "labels", "boxes"} - set(d)
     if missing:
@@ -409,29 +367,18 @@ def evaluate_masks(pred, gt, top_k=None, labels=None, min_voxels=1, fused=True):
     ``gt``: a dict in the layout of ``masks.load_3d_masks`` (``masks`` [k, W, L, H], ``labels`` [k], ``boxes`` [k, 6]) or
     the path of such an ``.npz``.  ``pred``: the same (with ``scores`` [k]), or the result of
     ``extract.extract_instances``: its label volume is scored directly (``label_mask_iou``, channel i + 1 = prediction
-    i), with the conventions of ``masks.write_instance_masks_npz`` - classes ``labels`` (default all ones), boxes =
-    inclusive voxel bounds with + 1 on the upper corner, and an instance below ``min_voxels`` voxels an empty mask with
-    score 0 and a zero box - so the result equals scoring the file that function writes.  With ``fused`` and a GPU
+    i), with the conventions of ``masks.instance_detections``, which ``masks.write_instance_masks_npz`` writes - classes
+    ``labels`` (default all ones), boxes = inclusive voxel bounds with + 1 on the upper corner, and an instance below
+    ``min_voxels`` voxels an empty mask with score 0 and a zero box - so the result equals scoring that file.  With ``fused`` and a GPU
     present, host arrays (files) are moved there and scored by the HIP kernels."""
     gt = _load_scene(gt, "evaluate_masks: gt")
-    g_masks, g_cls, g_boxes = gt["masks"], _as_tensor(gt["labels"]).cpu(), _as_tensor(gt["boxes"]).cpu().float()
+    g_masks, g_cls, g_boxes = gt["masks"], as_tensor(gt["labels"]).cpu(), as_tensor(gt["boxes"]).cpu().float()
     if fused and torch.cuda.is_available():                # host arrays (files) are scored on the GPU when there is one
-        g_masks = _as_tensor(g_masks).cuda()
+        g_masks = as_tensor(g_masks).cuda()
     if _is_extract_result(pred):
-        counts = _as_tensor(pred["counts"]).cpu()
-        k = int(counts.shape[0]) - 1
-        if k < 0:
-            raise ValueError("evaluate_masks: the extraction holds no instance channel")
-        keep = counts[1:] >= max(int(min_voxels), 1)
-        p_cls = torch.ones(k, dtype=torch.int64) if labels is None else _as_tensor(np.asarray(labels, dtype=np.int64)).reshape(-1)
-        if tuple(p_cls.shape) != (k,):
-            raise ValueError(f"labels must hold one class per instance id 1..{k}, got shape {tuple(p_cls.shape)}")
-        zero = torch.zeros(())
-        p_scores = torch.where(keep, _as_tensor(pred["scores"]).cpu()[1:].float(), zero)
-        p_boxes = _as_tensor(pred["boxes"]).cpu()[1:].float()
-        p_boxes[:, 3:] += 1.0
-        p_boxes = torch.where(keep.view(k, 1), p_boxes, zero)
-        inter, a1, a2 = label_mask_overlap(pred["labels"], k + 1, g_masks, 1, fused)
+        keep, p_cls, p_scores, p_boxes = (torch.from_numpy(a) for a in instance_detections(
+            pred, labels, min_voxels, who="evaluate_masks: the extraction"))
+        inter, a1, a2 = label_mask_overlap(pred["labels"], len(keep) + 1, g_masks, 1, fused)
         drop = ~keep.to(inter.device)
         inter[drop], a1[drop] = 0, 0
         iou = iou_from_counts(inter, a1, a2)
@@ -439,8 +386,8 @@ def evaluate_masks(pred, gt, top_k=None, labels=None, min_voxels=1, fused=True):
         pred = _load_scene(pred, "evaluate_masks: pred")
         if "scores" not in pred:
             raise ValueError("evaluate_masks: pred: missing key 'scores'")
-        p_cls, p_scores = _as_tensor(pred["labels"]).cpu(), _as_tensor(pred["scores"]).cpu().float()
-        p_boxes = _as_tensor(pred["boxes"]).cpu().float()
+        p_cls, p_scores = as_tensor(pred["labels"]).cpu(), as_tensor(pred["scores"]).cpu().float()
+        p_boxes = as_tensor(pred["boxes"]).cpu().float()
         n_p, n_g = len(p_cls), len(g_cls)
         iou = mask_iou_3d(pred["masks"], g_masks, fused=fused) if n_p and n_g else torch.zeros(n_p, n_g)
     iou = iou.cpu()

@@ -21,6 +21,8 @@ import contextlib
 import numpy as np
 import torch
 
+from . import _lib
+
 VIEW_DIRS = np.asarray([[1, 1, 1], [1, -1, -1], [-1, 1, -1], [-1, -1, 1]], dtype=np.float32) / np.sqrt(3.0)
 
 
@@ -207,7 +209,6 @@ def volume_stats(labels, confidence, K):
     (float64 sums)."""
     W, L, H = (int(v) for v in labels.shape)
     if labels.is_cuda and 1 <= K <= 64:
-        from . import _lib
         lib = _lib.load()
         dev = labels.device
         ws = torch.empty(_lib.INSTANCE_STATS_WORKSPACE_BYTES // 4, dtype=torch.int32, device=dev)
@@ -299,14 +300,12 @@ def _label_composable(labels, connectivity):
 def _workspace(nbytes, what, dtype, dev):
     """The caller-owned workspace of a library call, from the answer of its ``*_workspace_bytes`` export (negative: the
     export's error, raised as ``what``): -> (tensor of ``dtype``, nbytes)."""
-    from . import _lib
     nbytes = int(nbytes)
     _lib.check(min(nbytes, 0), what)
     return torch.empty(nbytes // dtype.itemsize, dtype=dtype, device=dev), nbytes
 
 
 def _label_hip(labels, connectivity):
-    from . import _lib
     lib = _lib.load()
     W, L, H = (int(v) for v in labels.shape)
     labels = labels.contiguous()
@@ -387,7 +386,6 @@ def filter_components(labels, confidence=None, K=None, connectivity=6, keep="lar
                                    confidence.device != labels.device):
         raise ValueError("filter_components: confidence must be float32, of the labels' shape and device")
     if labels.is_cuda and fused:
-        from . import _lib
         lib = _lib.load()
         W, L, H = (int(v) for v in labels.shape)
         labels, roots, ws, nbytes = _label_hip(labels, connectivity)
@@ -476,7 +474,6 @@ def mesh_from_lattice(field, iso, axes, ext, labels=None, select=-1, rgb=None, f
     for an axis of length 1; ``labels`` uint8 [W, L, H] with ``select`` = -1 or a channel; ``rgb`` float32 [W, L, H, 4]
     (channels 0..2 colour the vertices).  One host read-back of (V, F) between the two calls.
     -> dict vertices float32 [V, 3], faces int32 [F, 3], colors float32 [V, 3] / None, face_labels uint8 [F] / None."""
-    from . import _lib
     lib = _lib.load()
     if not field.is_cuda:
         raise RuntimeError("mesh_from_lattice: field must be a GPU tensor (the HIP path has no CPU fallback)")
@@ -514,8 +511,8 @@ def mesh_from_lattice(field, iso, axes, ext, labels=None, select=-1, rgb=None, f
     flab = torch.empty(F, dtype=torch.uint8, device=dev) if face_labels else None
     if V or F:
         _lib.check(lib.inr_mesh_emit(*head, P(rgb, allow_none=True), P(ax[0]), P(ax[1]), P(ax[2]), W, L, H, float(ext[0]),
-                                     float(ext[1]), float(ext[2]), cap, P(ws), nbytes, V, F, P(vertices, allow_none=V == 0),
-                                     P(faces, allow_none=F == 0), P(colors, allow_none=True), P(flab, allow_none=True),
+                                     float(ext[1]), float(ext[2]), cap, P(ws), nbytes, V, F, _lib.ptr_or_null(vertices),
+                                     _lib.ptr_or_null(faces), P(colors, allow_none=True), P(flab, allow_none=True),
                                      _lib.stream_ptr()), "mesh_emit")
     return {"vertices": vertices, "faces": faces, "colors": colors, "face_labels": flab}
 

@@ -15,6 +15,8 @@ f5  ``match_masks`` / ``project_and_match`` / ``match_seg_dir``: the matching st
     projected 3-D mask it overlaps best.  ``project_and_match`` feeds the projector's sums to the matcher without leaving
     the GPU; ``match_seg_dir`` is the drop-in for the script on one scene directory.
 """
+import contextlib
+import ctypes
 import json
 import os
 import struct
@@ -23,7 +25,10 @@ import zlib
 import numpy as np
 import torch
 
-from . import raymarching
+from . import _lib, hdf5_lite, raymarching
+from ._lib import check, ptr, ptr_or_null, stream_ptr
+from .extract import eval_mode
+from .maskbits import interleave32
 from .nerf.utils import get_rays
 
 
@@ -35,7 +40,6 @@ def load_matched_masks(seg_dir, names=None):
     """-> dict {image name: int32 [H, W]} from ``<seg_dir>/<name>.npy`` (match_seg.py:140) and, for images that only
     have it, from the ``<name>.hdf5`` mirror the reference writes beside it (match_seg.py:142-143: dataset
     ``cp_instance_id_segmaps``; read without h5py by ``hdf5_lite``).  When both exist the ``.npy`` file is read."""
-    from . import hdf5_lite
     listing = sorted(os.listdir(seg_dir))
     stems = {f[:-4]: f for f in listing if f.endswith(".npy")}
     for f in listing:
@@ -120,16 +124,8 @@ def load_3d_masks(path):
 
 def pack_mask_words(masks, device):
     """bool [k, W, L, H] -> list of int32 tensors [W, L, H], one per 32 masks: bit i of word j = mask 32 j + i contains
-    the voxel (the layout ``inr_project_masks_patch`` reads; int32 is the storage type, the kernel reads uint32)."""
-    m = torch.as_tensor(masks).to(device).bool()
-    out = []
-    for base in range(0, m.shape[0], 32):
-        chunk = m[base:base + 32].to(torch.int64)
-        shifts = torch.arange(chunk.shape[0], device=device, dtype=torch.int64).view(-1, 1, 1, 1)
-        w = (chunk << shifts).sum(0)
-        w = torch.where(w >= 2 ** 31, w - 2 ** 32, w)                 # the same 32 bits as a signed value
-        out.append(w.to(torch.int32).contiguous())
-    return out
+    the voxel (the voxel words of maskbits.py, which ``inr_project_masks_patch`` reads).  Plain torch on ``device``."""
+    return list(interleave32(torch.as_tensor(masks).to(device).bool()))
 
 
 @torch.no_grad()
@@ -143,8 +139,6 @@ def soft_project(model, masks, bbox_min, bbox_max, rays_o, rays_d, T_thresh=1e-4
     to the accumulators of the masks whose bit is set (``inr_project_masks_patch``; round 4 - until then the mask values
     of all samples were gathered into a float [M, k] matrix, 3.8 GB for an 800x800 frame and 30 masks, and composited as
     k extra channels: same sums in the same order, bit-identical)."""
-    from . import _lib
-    from ._lib import check, ptr, stream_ptr
     dev = rays_o.device
     k, words = packed if packed is not None else (len(masks), pack_mask_words(masks, dev))
     if k == 0:
@@ -163,13 +157,22 @@ def soft_project(model, masks, bbox_min, bbox_max, rays_o, rays_d, T_thresh=1e-4
     lib = _lib.load()
     for j, wj in enumerate(words):
         base = 32 * j
-        check(lib.inr_project_masks_patch(ptr(xyzs, torch.float32, "xyzs", allow_none=M == 0),
-                                          ptr(wbuf, torch.float32, "weights", allow_none=M == 0),
-                                          ptr(rays, torch.int32, "rays", allow_none=N == 0), N, M,
-                                          ptr(wj, torch.int32, "mask_words"), W, L, H,
-                                          _lib.host_ptr(bbox, torch.float32, "bbox"), k, base, min(32, k - base),
-                                          ptr(soft, allow_none=N == 0), stream_ptr()), "project_masks_patch")
+        check(lib.inr_project_masks_patch(ptr_or_null(xyzs, torch.float32, "xyzs"), ptr_or_null(wbuf, torch.float32, "weights"),
+                                          ptr_or_null(rays, torch.int32, "rays"), N, M, ptr(wj, torch.int32, "mask_words"),
+                                          W, L, H, _lib.host_ptr(bbox, torch.float32, "bbox"), k, base, min(32, k - base),
+                                          ptr_or_null(soft), stream_ptr()), "project_masks_patch")
     return soft, ws
+
+
+def _project_views(model, packed, bbox_min, bbox_max, poses, intrinsics, H, W):
+    """The view loop of the projector: yields ``(v, rays, soft)`` per pose - the view's ``get_rays`` dict (patch order when
+    H and W are multiples of 4) and the ``soft_project`` sums [H * W, k] of the ``packed`` masks over those rays.  The
+    model is in eval mode while the generator is open and gets its mode back when it is exhausted or closed; a consumer
+    holds it in ``contextlib.closing`` so that this also happens when the consumer raises."""
+    with eval_mode(model):
+        for v in range(poses.shape[0]):
+            r = get_rays(poses[v:v + 1], intrinsics, H, W, patch=4 if (H % 4 == 0 and W % 4 == 0) else 0)
+            yield v, r, soft_project(model, None, bbox_min, bbox_max, r["rays_o"][0], r["rays_d"][0], packed=packed)[0]
 
 
 @torch.no_grad()
@@ -183,24 +186,43 @@ def project_3d_masks(model, masks, bbox_min, bbox_max, poses, intrinsics, H, W, 
     poses = torch.as_tensor(poses).to(dev).float()
     k = len(masks) if packed is None else int(packed[0])
     out = np.zeros((poses.shape[0], k, H, W), dtype=bool)
-    was_training = model.training
-    model.eval()
     if packed is None:
         packed = (k, pack_mask_words(masks, dev))      # one 32-bit word per voxel and 32 masks, built once for all views
-    for v in range(poses.shape[0]):
-        r = get_rays(poses[v:v + 1], intrinsics, H, W, patch=4 if (H % 4 == 0 and W % 4 == 0) else 0)
-        soft, _ = soft_project(model, None, bbox_min, bbox_max, r["rays_o"][0], r["rays_d"][0], packed=packed)
-        flat = torch.zeros(H * W, k, device=dev)
-        flat[r["inds"][0]] = soft
-        out[v] = (flat > thresh).t().reshape(k, H, W).cpu().numpy()
-        if proj_dir is not None:
-            os.makedirs(proj_dir, exist_ok=True)
-            name = img_names[v] if img_names is not None else f"{v:04d}"
-            for i in range(k):
-                if out[v, i].any():
-                    save_png_gray(os.path.join(proj_dir, f"{name}_{i + 1}.png"), out[v, i].astype(np.uint8) * 255)
-    model.train(was_training)
+    with contextlib.closing(_project_views(model, packed, bbox_min, bbox_max, poses, intrinsics, H, W)) as views:
+        for v, r, soft in views:
+            flat = torch.zeros(H * W, k, device=dev)
+            flat[r["inds"][0]] = soft
+            out[v] = (flat > thresh).t().reshape(k, H, W).cpu().numpy()
+            if proj_dir is not None:
+                os.makedirs(proj_dir, exist_ok=True)
+                name = img_names[v] if img_names is not None else f"{v:04d}"
+                for i in range(k):
+                    if out[v, i].any():
+                        save_png_gray(os.path.join(proj_dir, f"{name}_{i + 1}.png"), out[v, i].astype(np.uint8) * 255)
     return out
+
+
+def instance_detections(result, labels=None, min_voxels=1, who="result"):
+    """The detections an ``extract.extract_instances`` result stands for, on the host: instance id i + 1 is detection i,
+    so k = K - 1 (channel 0, background / walls, is never one).  -> ``(keep bool [k], classes int64 [k], scores float32
+    [k], boxes float32 [k, 6])``: ``keep`` = the instance has at least ``min_voxels`` voxels; ``classes`` = the caller's
+    ``labels``, default all ones; boxes in grid units (min voxel index, max voxel index + 1); a dropped instance has score
+    0 and a zero box.  The one statement of what ``write_instance_masks_npz`` writes and ``evaluate.evaluate_masks``
+    scores."""
+    def host(v):
+        return v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
+    counts = host(result["counts"])
+    k = int(counts.shape[0]) - 1
+    if k < 0:
+        raise ValueError(f"{who} holds no instance channel")
+    cls = np.ones(k, dtype=np.int64) if labels is None else np.asarray(labels, dtype=np.int64).reshape(-1)
+    if cls.shape != (k,):
+        raise ValueError(f"labels must hold one class per instance id 1..{k}, got shape {cls.shape}")
+    keep = counts[1:] >= max(int(min_voxels), 1)
+    scores = np.where(keep, host(result["scores"])[1:], 0.0).astype(np.float32)
+    boxes = host(result["boxes"])[1:].astype(np.float32)
+    boxes[:, 3:] += 1.0
+    return keep, cls, scores, np.where(keep[:, None], boxes, np.float32(0.0))
 
 
 def write_instance_masks_npz(path, result, labels=None, min_voxels=1):
@@ -213,29 +235,16 @@ def write_instance_masks_npz(path, result, labels=None, min_voxels=1):
     never a mask.  The masks stay in ID ORDER, not sorted by score as the NeRF-RCNN writer sorts its detections, so that
     projecting and matching them reproduces the field's own ids.  An instance with fewer than ``min_voxels`` voxels keeps
     its slot with an empty mask, score 0 and a zero box.  -> path."""
-    def host(v):
-        return v.detach().cpu().numpy() if torch.is_tensor(v) else np.asarray(v)
-    lab = host(result["labels"])
+    lab = result["labels"]
+    lab = lab.detach().cpu().numpy() if torch.is_tensor(lab) else np.asarray(lab)
     if lab.ndim != 3:
         raise ValueError("result['labels'] must be [W, L, H]")
-    counts, boxes, scores = host(result["counts"]), host(result["boxes"]), host(result["scores"])
-    k = int(counts.shape[0]) - 1
-    if k < 0:
-        raise ValueError("result holds no instance channel")
-    cls = np.ones(k, dtype=np.int64) if labels is None else np.asarray(labels, dtype=np.int64).reshape(-1)
-    if cls.shape != (k,):
-        raise ValueError(f"labels must hold one class per instance id 1..{k}, got shape {cls.shape}")
-    keep = counts[1:] >= max(int(min_voxels), 1)
-    masks = np.zeros((k,) + lab.shape, dtype=bool)
+    keep, cls, scores, boxes = instance_detections(result, labels, min_voxels)
+    masks = np.zeros((len(keep),) + lab.shape, dtype=bool)
     for i in np.nonzero(keep)[0]:
         masks[i] = lab == i + 1
-    out_scores = np.where(keep, scores[1:], 0.0).astype(np.float32)
-    out_boxes = np.zeros((k, 6), dtype=np.float32)
-    b = boxes[1:].astype(np.float32)
-    out_boxes[keep, :3] = b[keep, :3]
-    out_boxes[keep, 3:] = b[keep, 3:] + 1.0
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    np.savez_compressed(path, masks=masks, scores=out_scores, labels=cls, boxes=out_boxes)
+    np.savez_compressed(path, masks=masks, scores=scores, labels=cls, boxes=boxes)
     return path
 
 
@@ -298,21 +307,13 @@ def select_projections(files, img_name):
 
 def pack_mask_bits(proj, device=None):
     """bool [n, k, H, W] (numpy or tensor) -> int32 tensor [n, ceil(k / 32), H, W] on ``device`` (default: where ``proj``
-    lives): bit j % 32 of word j // 32 = candidate j covers the pixel - the layout ``inr_match_count`` reads (int32 is the
-    storage type, the kernel reads uint32).  ``match_masks`` accepts the result in place of ``proj``."""
+    lives): bit j % 32 of word j // 32 = candidate j covers the pixel - the pixel words of maskbits.py, which
+    ``inr_match_count`` reads.  ``match_masks`` accepts the result in place of ``proj``."""
     m = torch.as_tensor(proj)
     if m.dtype != torch.bool or m.ndim != 4:
         raise ValueError("proj must be bool [n, k, H, W]")
     m = m.to(device if device is not None else m.device)
-    n, k, H, W = m.shape
-    out = torch.zeros(n, (k + 31) // 32, H, W, dtype=torch.int32, device=m.device)
-    for v in range(n):                                   # per view: the int64 staging is 32 words per pixel
-        for j in range(out.shape[1]):
-            chunk = m[v, 32 * j:32 * j + 32].to(torch.int64)
-            shifts = torch.arange(chunk.shape[0], device=m.device, dtype=torch.int64).view(-1, 1, 1)
-            w = (chunk << shifts).sum(0)
-            out[v, j] = torch.where(w >= 2 ** 31, w - 2 ** 32, w).to(torch.int32)
-    return out
+    return interleave32(m.transpose(0, 1)).transpose(0, 1).contiguous()
 
 
 def _rank_segments(seg):
@@ -354,9 +355,6 @@ def match_ranked(ranks, words, S, k, instance_ids, iou_thresh=0.05):
     """The two device calls (include/inr.h, "2-D mask matching") on ranked maps: ranks int32 [n, P] (-1, 0 or a rank
     1..S), words int32 [n, ceil(k / 32), P] (``pack_mask_bits`` layout; ignored when k = 0), instance_ids int32 tensor [k]
     in candidate order.  -> int32 [n, P].  One read-back after both calls: a rank outside [-1, S] raises ValueError."""
-    from . import _lib
-    from ._lib import check, ptr, stream_ptr
-    import ctypes
     n, P = (int(v) for v in ranks.shape)
     dev = ranks.device
     lib = _lib.load()
@@ -369,14 +367,12 @@ def match_ranked(ranks, words, S, k, instance_ids, iou_thresh=0.05):
     status = torch.empty(1, dtype=torch.int32, device=dev)
     assigned = torch.empty(n, S + 1, dtype=torch.int32, device=dev)
     out = torch.empty(n, P, dtype=torch.int32, device=dev)
-    none = k == 0
-    check(lib.inr_match_count(ptr(ranks, torch.int32, "ranks"), ptr(None if none else words, torch.int32, "words", allow_none=none),
-                              n, P, S, k, ptr(seg_area), ptr(None if none else mask_area, allow_none=none),
-                              ptr(None if none else inter, allow_none=none), ptr(status), stream_ptr()), "match_count")
+    check(lib.inr_match_count(ptr(ranks, torch.int32, "ranks"), ptr(words, torch.int32, "words") if k > 0 else None,
+                              n, P, S, k, ptr(seg_area), ptr_or_null(mask_area), ptr_or_null(inter), ptr(status), stream_ptr()),
+          "match_count")
     thresh = ctypes.c_double(float(iou_thresh))
-    check(lib.inr_match_assign(ptr(ranks), ptr(seg_area), ptr(None if none else mask_area, allow_none=none),
-                               ptr(None if none else inter, allow_none=none),
-                               ptr(None if none else instance_ids, torch.int32, "instance_ids", allow_none=none), n, P, S, k,
+    check(lib.inr_match_assign(ptr(ranks), ptr(seg_area), ptr_or_null(mask_area), ptr_or_null(inter),
+                               ptr_or_null(instance_ids, torch.int32, "instance_ids"), n, P, S, k,
                                ctypes.cast(ctypes.pointer(thresh), ctypes.c_void_p), ptr(assigned), ptr(out), stream_ptr()),
           "match_assign")
     if int(status) != 0:
@@ -494,8 +490,6 @@ def project_and_match(model, masks, bbox_min, bbox_max, poses, intrinsics, H, W,
     ``packed``: ``(k, words)`` handed to ``soft_project`` in place of ``masks`` (which may then be None); the words must
     hold the masks in CANDIDATE ORDER (``candidate_order(range(1, k + 1))``, the ``order`` argument of
     ``detections.planes_to_voxel_words``)."""
-    from . import _lib
-    from ._lib import check, ptr, stream_ptr
     dev = next(model.parameters()).device
     poses = torch.as_tensor(poses).to(dev).float()
     n, k = int(poses.shape[0]), len(masks) if packed is None else int(packed[0])
@@ -505,18 +499,14 @@ def project_and_match(model, masks, bbox_min, bbox_max, poses, intrinsics, H, W,
     ids = [i + 1 for i in order]
     nw, P = (k + 31) // 32, H * W
     words = torch.empty(n, nw, H, W, dtype=torch.int32, device=dev)
-    was_training = model.training
-    model.eval()
     if packed is None:
         packed = (k, pack_mask_words(torch.as_tensor(masks)[torch.as_tensor(order)], dev))
     lib = _lib.load()
-    for v in range(n):
-        r = get_rays(poses[v:v + 1], intrinsics, H, W, patch=4 if (H % 4 == 0 and W % 4 == 0) else 0)
-        soft, _ = soft_project(model, None, bbox_min, bbox_max, r["rays_o"][0], r["rays_d"][0], packed=packed)
-        inds = r["inds"][0].contiguous()
-        check(lib.inr_pack_mask_bits(ptr(soft, torch.float32, "soft"), ptr(inds, torch.int64, "inds"), int(soft.shape[0]), k,
-                                     float(thresh), P, ptr(words[v]), stream_ptr()), "pack_mask_bits")
-    model.train(was_training)
+    with contextlib.closing(_project_views(model, packed, bbox_min, bbox_max, poses, intrinsics, H, W)) as views:
+        for v, r, soft in views:
+            inds = r["inds"][0].contiguous()
+            check(lib.inr_pack_mask_bits(ptr(soft, torch.float32, "soft"), ptr(inds, torch.int64, "inds"), int(soft.shape[0]), k,
+                                         float(thresh), P, ptr(words[v]), stream_ptr()), "pack_mask_bits")
     seg = seg_maps if torch.is_tensor(seg_maps) else torch.from_numpy(np.ascontiguousarray(seg_maps).astype(np.int32))
     out = match_masks(seg.to(dev), words, instance_ids=ids, iou_thresh=iou_thresh, fused=True, ordered=True)
     if out_dir is not None:

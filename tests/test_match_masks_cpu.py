@@ -137,6 +137,34 @@ def test_packed_words_round_trip_and_match():
         run(seg, pack_mask_bits(proj), np.arange(1, 34))                   # 1, 2, ..: "10.png" sorts before "2.png"
 
 
+# ---- the projector's view loop -----------------------------------------------------------------------------------------
+def test_view_loop_restores_the_model_mode_when_its_consumer_raises(monkeypatch, tmp_path):
+    """``project_3d_masks`` consumes the view loop; a failure while it writes a view's PNGs must not leave the model in
+    eval mode.  The projector itself is stubbed (it needs a GPU): every pixel of every view is inside the one mask."""
+    from instance_nerf_amd import masks as pm
+    H = W = 2
+    modes = []
+
+    def rays(*a, **k):
+        return {"rays_o": [None], "rays_d": [None], "inds": [torch.arange(H * W)]}
+
+    def project(model, *a, **k):
+        modes.append(model.training)
+        return torch.ones(H * W, 1), None
+
+    def fail(*a, **k):
+        raise OSError("disk full")
+    monkeypatch.setattr(pm, "get_rays", rays)
+    monkeypatch.setattr(pm, "soft_project", project)
+    model = torch.nn.Linear(1, 1).train()
+    out = pm.project_3d_masks(model, None, None, None, torch.zeros(2, 4, 4), None, H, W, packed=(1, None))
+    assert out.all() and modes == [False, False] and model.training
+    monkeypatch.setattr(pm, "save_png_gray", fail)
+    with pytest.raises(OSError, match="disk full") as err:
+        pm.project_3d_masks(model, None, None, None, torch.zeros(2, 4, 4), None, H, W, proj_dir=str(tmp_path), packed=(1, None))
+    assert model.training and modes == [False] * 3, err
+
+
 # ---- convert_segments --------------------------------------------------------------------------------------------------
 def test_convert_segments():
     from instance_nerf_amd.masks import BACKGROUND_STUFF, convert_segments
