@@ -775,6 +775,34 @@ int inr_roi_align_3d_backward_ws(const float* grad_out, const float* rois, const
                                  int32_t out_l, int32_t out_h, float spatial_scale, float* grad_input,
                                  void* workspace, int64_t workspace_bytes, inr_stream_t s);
 
+/* No reference counterpart as a native call: the reference's MultiScaleRoIAlign3D
+ * (/root/reference/nerf_rcnn/model/poolers.py:115-188) pools from a feature pyramid with one roi_align_3d call per level
+ * between host-synchronising index operations.  The pyramid form does it in ONE launch: every RoI names its level,
+ * roi_levels int32 [K] (device), and row k of out [K,C,out_w,out_l,out_h] is RoI k whatever its level.  The level table
+ * arrives as plain HOST arrays - level_ptrs [n_levels] device pointers of the volumes [N,C,W,L,H] (the same N and C on
+ * every level), level_dims int32 [n_levels*3] = (W, L, H) per level, level_scales [n_levels] - and travels in the kernel
+ * arguments: nothing is copied to the device or read back.  1 <= n_levels <= INR_ROI_MAX_LEVELS.  order int32 [K]
+ * (device, nullable): the RoI that the i-th workgroup slot handles, a permutation of 0..K-1 - pass the stable argsort of
+ * roi_levels, so that the workgroups resident at one time read one level (an entry outside [0, K) is ignored; the
+ * lane-per-output kernels do not use it).  A RoI whose level is outside [0, n_levels) gives a row of zeros in the
+ * forward and adds nothing in the backward.  Same arithmetic as inr_roi_align_3d_forward / _backward on the RoI's level:
+ * the forward's rows carry the same bits.  Kernels (inr_roi_align_3d_set_mode): the separable ones if EVERY level fits
+ * them, else one lane per output element; mode 2: INR_EINVAL naming the level that does not fit.
+ * backward: level_grads [n_levels] are the grad_input volumes, ACCUMULATED into (the caller zeroes them); a null entry
+ * = that level needs no gradient, its RoIs are skipped.  Always the in-place form (no workspace variant).
+ * K == 0: INR_OK, nothing launched.  Limits: N, K >= 0, C, out_* >= 1, K*C*out_w*out_l*out_h < 2^39; INR_EINVAL beyond. */
+#define INR_ROI_MAX_LEVELS 8
+int inr_roi_align_3d_pyramid_forward(const float* const* level_ptrs /*host*/, const int32_t* level_dims /*host*/,
+                                     const float* level_scales /*host*/, int32_t n_levels, const float* rois,
+                                     const int32_t* roi_inds, const int32_t* roi_levels, const int32_t* order /*nullable*/,
+                                     int32_t N, int32_t C, int64_t K, int32_t out_w, int32_t out_l, int32_t out_h,
+                                     float* out, inr_stream_t s);
+int inr_roi_align_3d_pyramid_backward(float* const* level_grads /*host*/, const int32_t* level_dims /*host*/,
+                                      const float* level_scales /*host*/, int32_t n_levels, const float* rois,
+                                      const int32_t* roi_inds, const int32_t* roi_levels, const int32_t* order /*nullable*/,
+                                      int32_t N, int32_t C, int64_t K, int32_t out_w, int32_t out_l, int32_t out_h,
+                                      const float* grad_out, inr_stream_t s);
+
 /* Whole-ray rendering with early termination (inference, patch-interleaved layout): field evaluation and alpha
  * compositing in one launch; a 16-ray group stops being evaluated once all its rays are below T_thresh (what the
  * alive-ray loop of NeRFRenderer.run_cuda achieves, a5, without host round trips).  Same results as

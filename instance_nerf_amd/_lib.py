@@ -16,6 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("INR_LIB_PATH") or os.path.join(_HERE, "csrc", "libinr_hip.so")   # env override: profiling builds only
 MAX_LEVELS = 16
 GRID_FX_STATE_FLOATS = 4192      # include/inr.h INR_GRID_FX_STATE_FLOATS
+ROI_MAX_LEVELS = 8               # include/inr.h INR_ROI_MAX_LEVELS
 NUMERICS_TABLE_F16, NUMERICS_MLP_F16 = 1, 2      # include/inr.h INR_NUMERICS_*
 
 
@@ -146,6 +147,10 @@ _SIGS = {
                                                               c_int32, c_int32, c_int64]),
     "inr_roi_align_3d_backward_ws": (c_int32, [P, P, P, c_int32, c_int32, c_int32, c_int32, c_int32, c_int64, c_int32,
                                                c_int32, c_int32, c_float, P, P, c_int64, P]),
+    "inr_roi_align_3d_pyramid_forward": (c_int32, [P, P, P, c_int32, P, P, P, P, c_int32, c_int32, c_int64, c_int32,
+                                                   c_int32, c_int32, P, P]),
+    "inr_roi_align_3d_pyramid_backward": (c_int32, [P, P, P, c_int32, P, P, P, P, c_int32, c_int32, c_int64, c_int32,
+                                                    c_int32, c_int32, P, P]),
     "inr_nerf_render": (c_int32, [P, P, P, P, c_int64, c_int64, c_float, P, POINTER(GridDesc), P, c_float, c_float,
                                   P, P, P, P, P, c_int32, c_int32, P]),
     "inr_instance_render": (c_int32, [P, P, P, c_int64, c_int64, c_float, P, POINTER(GridDesc), P, c_int32, P, c_int32, P,

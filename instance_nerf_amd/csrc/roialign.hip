@@ -17,6 +17,11 @@
 //    an XCD at a time share ONE run of channels (2 MB of the volume: stays in that XCD's 4 MB L2).
 //  * one lane per output element (rounds 1-3, the torchvision kernel shape): kept for shapes whose tables do not
 //    fit the LDS budget and as the A/B the tests compare with (inr_roi_align_3d_set_mode).
+// Both also come in a PYRAMID form (inr_roi_align_3d_pyramid_forward / _backward): the reference's callers pool from a
+// feature pyramid (model/poolers.py:115-188: per level a torch.where read-back, a gather, one call, an indexed scatter),
+// and there one launch handles the RoIs of all levels - the same kernel bodies, with the extents, scale and base pointer
+// of a workgroup's volume taken from a level table in the kernel arguments, indexed by roi_levels[k]; row k of the
+// output is RoI k, so nothing is gathered or scattered and nothing is read back.
 #include "common.h"
 
 namespace inr {
@@ -65,12 +70,12 @@ __device__ __forceinline__ Tri tri_setup(float x, float y, float z, int W, int L
   return t;
 }
 
-__global__ void __launch_bounds__(256) k_roi_align3d_fwd(const float* __restrict__ in, const float* __restrict__ rois,
-                                                         const int32_t* __restrict__ roi_inds, int C, int W, int L,
-                                                         int H, int64_t total, int ow, int ol, int oh, float scale,
-                                                         float* __restrict__ out) {
-  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (idx >= total) return;
+// Output element idx of the lane-per-output forward; `in` is the volume the RoI's level names (the pyramid kernel
+// below calls this with the extents, scale and base pointer of roi_levels[k]).
+__device__ __forceinline__ void roi_fwd_elem(const float* __restrict__ in, const float* __restrict__ rois,
+                                             const int32_t* __restrict__ roi_inds, int C, int W, int L, int H,
+                                             int64_t idx, int ow, int ol, int oh, float scale,
+                                             float* __restrict__ out) {
   const int ph = (int)(idx % oh), pl = (int)((idx / oh) % ol), pw = (int)((idx / ((int64_t)oh * ol)) % ow);
   const int c = (int)((idx / ((int64_t)oh * ol * ow)) % C);
   const int64_t k = idx / ((int64_t)oh * ol * ow * C);
@@ -98,12 +103,19 @@ __global__ void __launch_bounds__(256) k_roi_align3d_fwd(const float* __restrict
   out[idx] = acc * g.inv_count;
 }
 
-__global__ void __launch_bounds__(256) k_roi_align3d_bwd(const float* __restrict__ gout, const float* __restrict__ rois,
+__global__ void __launch_bounds__(256) k_roi_align3d_fwd(const float* __restrict__ in, const float* __restrict__ rois,
                                                          const int32_t* __restrict__ roi_inds, int C, int W, int L,
                                                          int H, int64_t total, int ow, int ol, int oh, float scale,
-                                                         float* __restrict__ gin) {
+                                                         float* __restrict__ out) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= total) return;
+  roi_fwd_elem(in, rois, roi_inds, C, W, L, H, idx, ow, ol, oh, scale, out);
+}
+
+__device__ __forceinline__ void roi_bwd_elem(const float* __restrict__ gout, const float* __restrict__ rois,
+                                             const int32_t* __restrict__ roi_inds, int C, int W, int L, int H,
+                                             int64_t idx, int ow, int ol, int oh, float scale,
+                                             float* __restrict__ gin) {
   const int ph = (int)(idx % oh), pl = (int)((idx / oh) % ol), pw = (int)((idx / ((int64_t)oh * ol)) % ow);
   const int c = (int)((idx / ((int64_t)oh * ol * ow)) % C);
   const int64_t k = idx / ((int64_t)oh * ol * ow * C);
@@ -129,6 +141,73 @@ __global__ void __launch_bounds__(256) k_roi_align3d_bwd(const float* __restrict
       }
     }
   }
+}
+
+__global__ void __launch_bounds__(256) k_roi_align3d_bwd(const float* __restrict__ gout, const float* __restrict__ rois,
+                                                         const int32_t* __restrict__ roi_inds, int C, int W, int L,
+                                                         int H, int64_t total, int ow, int ol, int oh, float scale,
+                                                         float* __restrict__ gin) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  roi_bwd_elem(gout, rois, roi_inds, C, W, L, H, idx, ow, ol, oh, scale, gin);
+}
+
+// ---- pyramid form: one launch pools RoIs from several volumes (the levels of a feature pyramid) ---------------------
+// The level table travels by value in the kernel arguments and is indexed by roi_levels[k]: no copy of it to the device,
+// nothing read back.  Row k of the output is row k of the RoIs whatever its level, so there is no per-level result to
+// scatter.  A level outside [0, n) never touches the table: zeros in the forward, nothing added in the backward.
+struct PyrLevel {
+  float* ptr;        // the level's volume [N,C,W,L,H] (forward: read only; backward: its grad_input, null = no gradient)
+  int W, L, H;
+  float scale;
+  int tmp_floats;    // separable kernels: the slab budget sep_lds_bytes gives this level on its own
+  int pad;
+};
+struct PyrTable {
+  PyrLevel lv[INR_ROI_MAX_LEVELS];
+  int n;
+};
+
+// Entry lv of the table, read where the kernel arguments live: the table is the FIRST argument of every pyramid kernel,
+// so it starts at offset 0 of the kernel-argument segment (constant address space: a scalar load for the wave-uniform
+// index of the separable kernels, a vector load per lane otherwise).  Indexing the by-value argument itself - a loop over
+// the entries or a chain of selects alike - makes the compiler keep a private copy of the whole table in scratch memory
+// (200-256 bytes per lane, found in the ISA).
+typedef __attribute__((address_space(4))) const PyrLevel cPyrLevel;
+__device__ __forceinline__ PyrLevel pyr_level(int lv) {
+  static_assert(offsetof(PyrTable, lv) == 0, "the level table must start the kernel arguments");
+  cPyrLevel* tab = (cPyrLevel*)__builtin_amdgcn_kernarg_segment_ptr();
+  PyrLevel e;
+  e.ptr = tab[lv].ptr; e.W = tab[lv].W; e.L = tab[lv].L; e.H = tab[lv].H;
+  e.scale = tab[lv].scale; e.tmp_floats = tab[lv].tmp_floats; e.pad = 0;
+  return e;
+}
+
+__global__ void __launch_bounds__(256) k_roi_align3d_pyr_fwd(PyrTable P, const float* __restrict__ rois,
+                                                             const int32_t* __restrict__ roi_inds,
+                                                             const int32_t* __restrict__ roi_levels, int C,
+                                                             int64_t total, int ow, int ol, int oh,
+                                                             float* __restrict__ out) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int lv = roi_levels[idx / ((int64_t)oh * ol * ow * C)];
+  if ((unsigned)lv >= (unsigned)P.n) { out[idx] = 0.0f; return; }
+  const PyrLevel e = pyr_level(lv);
+  roi_fwd_elem(e.ptr, rois, roi_inds, C, e.W, e.L, e.H, idx, ow, ol, oh, e.scale, out);
+}
+
+__global__ void __launch_bounds__(256) k_roi_align3d_pyr_bwd(PyrTable P, const float* __restrict__ gout,
+                                                             const float* __restrict__ rois,
+                                                             const int32_t* __restrict__ roi_inds,
+                                                             const int32_t* __restrict__ roi_levels, int C,
+                                                             int64_t total, int ow, int ol, int oh) {
+  const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= total) return;
+  const int lv = roi_levels[idx / ((int64_t)oh * ol * ow * C)];
+  if ((unsigned)lv >= (unsigned)P.n) return;
+  const PyrLevel e = pyr_level(lv);
+  if (!e.ptr) return;
+  roi_bwd_elem(gout, rois, roi_inds, C, e.W, e.L, e.H, idx, ow, ol, oh, e.scale, e.ptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -274,14 +353,13 @@ __device__ __forceinline__ void fma4(f32x4& a, float w, const f32x4 v) {
 // The kernel is bound by vector-instruction issue (PMC, profiles/r04_roialign_pmc.txt: a wave64 instruction holds a
 // SIMD for four cycles), so instructions per element are what is trimmed: buffer loads (one 32-bit offset per row
 // for all four channels, the channel in the scalar offset), explicit fma, no index decoding in the inner loops.
+// (k, c0): the RoI and the first channel of the workgroup (sep_assign); A: the extents, scale and slab budget of the
+// volume `in` - the kernel's arguments, or in the pyramid kernel those of the RoI's level.
 template <int NOUT, bool kMulti>   // NOUT output elements per thread; kMulti: outputs beyond NOUT * SEP_THREADS, in chunks
-__global__ void __launch_bounds__(SEP_THREADS) k_roi_align3d_sep_fwd(const float* __restrict__ in,
-                                                                     const float* __restrict__ rois,
-                                                                     const int32_t* __restrict__ roi_inds, SepArgs A,
-                                                                     float* __restrict__ out) {
+__device__ __forceinline__ void sep_fwd_body(const float* __restrict__ in, const float* __restrict__ rois,
+                                             const int32_t* __restrict__ roi_inds, const SepArgs& A, const int k,
+                                             const int c0, float* __restrict__ out) {
   extern __shared__ f32x4 lds4[];
-  int k, c0;
-  if (!sep_assign(A, &k, &c0)) return;
   lfloat* lds = (lfloat*)lds4;
   const int t = threadIdx.x;
   const int W = A.W, L = A.L, H = A.H, ow = A.ow, ol = A.ol, oh = A.oh;
@@ -515,6 +593,52 @@ __global__ void __launch_bounds__(SEP_THREADS) k_roi_align3d_sep_fwd(const float
   }
 }
 
+template <int NOUT, bool kMulti>
+__global__ void __launch_bounds__(SEP_THREADS) k_roi_align3d_sep_fwd(const float* __restrict__ in,
+                                                                     const float* __restrict__ rois,
+                                                                     const int32_t* __restrict__ roi_inds, SepArgs A,
+                                                                     float* __restrict__ out) {
+  int k, c0;
+  if (!sep_assign(A, &k, &c0)) return;
+  sep_fwd_body<NOUT, kMulti>(in, rois, roi_inds, A, k, c0, out);
+}
+
+// The pyramid kernels' share of sep_assign: slot -> RoI through `order` (the host passes the stable argsort of the
+// levels, so the workgroups resident on an XCD at a time read one level's channel run), then the RoI's level into A.
+// false: nothing to pool (a level outside the table; an `order` entry outside [0, K) owns no row at all: *k < 0).
+__device__ __forceinline__ bool pyr_assign(const PyrTable& P, const int32_t* __restrict__ roi_levels,
+                                           const int32_t* __restrict__ order, SepArgs& A, int* k, float** vol) {
+  if (order) {
+    *k = __builtin_amdgcn_readfirstlane(order[*k]);
+    if ((unsigned)*k >= (unsigned)A.K) { *k = -1; return false; }
+  }
+  const int lv = __builtin_amdgcn_readfirstlane(roi_levels[*k]);
+  if ((unsigned)lv >= (unsigned)P.n) return false;
+  const PyrLevel e = pyr_level(lv);
+  A.W = e.W; A.L = e.L; A.H = e.H; A.scale = e.scale; A.tmp_floats = e.tmp_floats;
+  *vol = e.ptr;
+  return true;
+}
+
+template <int NOUT, bool kMulti>
+__global__ void __launch_bounds__(SEP_THREADS) k_roi_align3d_sep_pyr_fwd(PyrTable P, const float* __restrict__ rois,
+                                                                         const int32_t* __restrict__ roi_inds,
+                                                                         const int32_t* __restrict__ roi_levels,
+                                                                         const int32_t* __restrict__ order, SepArgs A,
+                                                                         float* __restrict__ out) {
+  int k, c0;
+  if (!sep_assign(A, &k, &c0)) return;
+  float* vol;
+  if (!pyr_assign(P, roi_levels, order, A, &k, &vol)) {
+    if (k < 0) return;
+    const int nout = A.ow * A.ol * A.oh, nch = min(c0 + A.cpb, A.C) - c0;      // the row's channel run: zeros
+    float* dst = out + ((int64_t)k * A.C + c0) * nout;
+    for (int o = threadIdx.x; o < nch * nout; o += SEP_THREADS) dst[o] = 0.0f;
+    return;
+  }
+  sep_fwd_body<NOUT, kMulti>(vol, rois, roi_inds, A, k, c0, out);
+}
+
 // Backward = the transpose, pass by pass: gout [ow][ol][oh] -(x^T)-> [sx][ol][oh] -(y^T)-> [sx][sy][oh] -(z^T)->
 // [sx][sy][sz], added into grad_input with one atomic per touched cell and channel (the lane-per-output kernel
 // issues 8 g^3 per output element); lanes run along z, so the atomics of a wave hit adjacent addresses.
@@ -526,13 +650,10 @@ __global__ void __launch_bounds__(SEP_THREADS) k_roi_align3d_sep_fwd(const float
 // layout of the accumulation target: k_roi_align3d_sep_bwd_cl below (channels fastest: one 64-byte request per voxel and
 // 16 channels, plus a transposing copy into grad_input; 0.34 ms for the whole call) is what inr_roi_align_3d_backward_ws
 // runs; this kernel stays behind inr_roi_align_3d_backward (no workspace, accumulates in place, any channel count).
-__global__ void __launch_bounds__(SEP_THREADS) k_roi_align3d_sep_bwd(const float* __restrict__ gout,
-                                                                     const float* __restrict__ rois,
-                                                                     const int32_t* __restrict__ roi_inds, SepArgs A,
-                                                                     float* __restrict__ gin) {
+__device__ __forceinline__ void sep_bwd_body(const float* __restrict__ gout, const float* __restrict__ rois,
+                                             const int32_t* __restrict__ roi_inds, const SepArgs& A, const int k,
+                                             const int c0, float* __restrict__ gin) {
   extern __shared__ f32x4 lds4[];
-  int k, c0;
-  if (!sep_assign(A, &k, &c0)) return;
   lfloat* lds = (lfloat*)lds4;
   const int t = threadIdx.x;
   const int W = A.W, L = A.L, H = A.H, ow = A.ow, ol = A.ol, oh = A.oh;
@@ -780,6 +901,28 @@ __global__ void __launch_bounds__(SEP_THREADS) k_roi_align3d_sep_bwd(const float
     }
     __syncthreads();   // go is reloaded
   }
+}
+
+__global__ void __launch_bounds__(SEP_THREADS) k_roi_align3d_sep_bwd(const float* __restrict__ gout,
+                                                                     const float* __restrict__ rois,
+                                                                     const int32_t* __restrict__ roi_inds, SepArgs A,
+                                                                     float* __restrict__ gin) {
+  int k, c0;
+  if (!sep_assign(A, &k, &c0)) return;
+  sep_bwd_body(gout, rois, roi_inds, A, k, c0, gin);
+}
+
+// pyramid form: accumulates into the grad_input of the RoI's level (a null one: that level needs no gradient)
+__global__ void __launch_bounds__(SEP_THREADS) k_roi_align3d_sep_pyr_bwd(PyrTable P, const float* __restrict__ gout,
+                                                                         const float* __restrict__ rois,
+                                                                         const int32_t* __restrict__ roi_inds,
+                                                                         const int32_t* __restrict__ roi_levels,
+                                                                         const int32_t* __restrict__ order, SepArgs A) {
+  int k, c0;
+  if (!sep_assign(A, &k, &c0)) return;
+  float* gin;
+  if (!pyr_assign(P, roi_levels, order, A, &k, &gin) || !gin) return;
+  sep_bwd_body(gout, rois, roi_inds, A, k, c0, gin);
 }
 
 // ---- backward with a channels-fastest accumulation target (round 5) ---------------------------------------------------
@@ -1075,6 +1218,133 @@ int inr_roi_align_3d_backward(const float* grad_out, const float* rois, const in
   k_roi_align3d_bwd<<<blocks_for(total, 256), 256, 0, as_stream(s)>>>(grad_out, rois, roi_inds, C, W, L, H, total,
                                                                       out_w, out_l, out_h, spatial_scale, grad_input);
   return check_launch("roi_align_3d_backward");
+}
+
+// ---- pyramid form (MultiScaleRoIAlign3D in one launch) -----------------------------------------------------------------
+// Validates the arguments both pyramid calls share - before any host array is read - and fills the level table.
+// 1: go on; 0: nothing to do (K == 0); < 0: error.  ptr_required: the forward needs every level's volume, the backward
+// takes a null grad_input as "no gradient for this level".
+static int pyr_prepare(const char* fn, const void* const* level_ptrs, const int32_t* level_dims, const float* level_scales,
+                       int32_t n_levels, const void* rois, const void* roi_inds, const void* roi_levels, const void* io,
+                       int32_t N, int32_t C, int64_t K, int32_t out_w, int32_t out_l, int32_t out_h, bool ptr_required,
+                       PyrTable* P) {
+  if (n_levels < 1 || n_levels > INR_ROI_MAX_LEVELS) {
+    set_error("%s: n_levels must be 1..%d (INR_ROI_MAX_LEVELS)", fn, INR_ROI_MAX_LEVELS);
+    return INR_EINVAL;
+  }
+  if (K < 0 || N < 0 || C <= 0) { set_error("%s: bad sizes (N, K >= 0, C > 0)", fn); return INR_EINVAL; }
+  if (out_w <= 0 || out_l <= 0 || out_h <= 0) {
+    set_error("%s: bad sizes (out_w, out_l, out_h must be positive)", fn);
+    return INR_EINVAL;
+  }
+  if (K == 0) return 0;
+  if (!level_ptrs || !level_dims || !level_scales || !rois || !roi_inds || !roi_levels || !io || N <= 0) {
+    set_error("%s: null pointer", fn);
+    return INR_EINVAL;
+  }
+  const int64_t nout = (int64_t)out_w * out_l * out_h;
+  if (K >= (1ll << 31) || K * C >= (1ll << 62) / nout || (K * C * nout + 255) / 256 >= (1ll << 31)) {
+    set_error("%s: K * C * out_w * out_l * out_h is beyond one launch", fn);
+    return INR_EINVAL;
+  }
+  P->n = n_levels;
+  for (int l = 0; l < INR_ROI_MAX_LEVELS; ++l) {
+    PyrLevel& e = P->lv[l];
+    e = PyrLevel{nullptr, 1, 1, 1, 0.0f, 0, 0};
+    if (l >= n_levels) continue;
+    e.W = level_dims[3 * l]; e.L = level_dims[3 * l + 1]; e.H = level_dims[3 * l + 2];
+    e.scale = level_scales[l];
+    e.ptr = static_cast<float*>(const_cast<void*>(level_ptrs[l]));
+    if (e.W <= 0 || e.L <= 0 || e.H <= 0) { set_error("%s: level_dims of level %d: bad sizes", fn, l); return INR_EINVAL; }
+    if (ptr_required && !e.ptr) { set_error("%s: level_ptrs[%d] is a null pointer", fn, l); return INR_EINVAL; }
+  }
+  return 1;
+}
+
+int inr_roi_align_3d_pyramid_forward(const float* const* level_ptrs, const int32_t* level_dims, const float* level_scales,
+                                     int32_t n_levels, const float* rois, const int32_t* roi_inds,
+                                     const int32_t* roi_levels, const int32_t* order, int32_t N, int32_t C, int64_t K,
+                                     int32_t out_w, int32_t out_l, int32_t out_h, float* out, inr_stream_t s) {
+  PyrTable P;
+  const int rc = pyr_prepare(__func__, reinterpret_cast<const void* const*>(level_ptrs), level_dims, level_scales, n_levels,
+                             rois, roi_inds, roi_levels, out, N, C, K, out_w, out_l, out_h, true, &P);
+  if (rc <= 0) return rc;
+  const int64_t nout = (int64_t)out_w * out_l * out_h;
+  // the separable kernels if EVERY level fits them (the conditions of inr_roi_align_3d_forward, per level); the dynamic
+  // LDS of the launch is the largest level's, each level keeps the slab budget it has on its own
+  const bool sep_shape = nout <= 16 * SEP_THREADS && (int64_t)out_l * out_h <= SEP_THREADS && sep_grid_fits(C, K);
+  int lds = 0, misfit = -1;
+  for (int l = 0; l < n_levels && misfit < 0; ++l) {
+    PyrLevel& e = P.lv[l];
+    const bool ok = sep_shape && e.H >= 4 && (int64_t)C * e.W * e.L * e.H * 4 < (1ll << 31);
+    const int b = ok ? sep_lds_bytes(e.W, e.L, e.H, out_w, out_l, out_h, false, &e.tmp_floats) : 0;
+    if (b <= 0) misfit = l;
+    lds = std::max(lds, b);
+  }
+  if (g_roi_mode == 2 && misfit >= 0) {
+    set_error("%s: separable kernel: level %d does not fit it (H >= 4, tables within the LDS window, C*W*L*H*4 < 2^31)",
+              __func__, misfit);
+    return INR_EINVAL;
+  }
+  if (g_roi_mode != 1 && misfit < 0) {
+    SepArgs A;
+    A.C = C; A.W = 0; A.L = 0; A.H = 0; A.ow = out_w; A.ol = out_l; A.oh = out_h; A.scale = 0.0f;      // per level: the table
+    A.cpb = sep_channels_per_block(C, K);
+    A.ngroups = (C + A.cpb - 1) / A.cpb;
+    A.K = (int)K;
+    A.tmp_floats = 0;
+    const unsigned grid = 8u * (unsigned)K * (unsigned)((A.ngroups + 7) / 8);
+    if (nout <= 4 * SEP_THREADS)
+      k_roi_align3d_sep_pyr_fwd<4, false><<<grid, SEP_THREADS, lds, as_stream(s)>>>(P, rois, roi_inds, roi_levels, order, A, out);
+    else
+      k_roi_align3d_sep_pyr_fwd<4, true><<<grid, SEP_THREADS, lds, as_stream(s)>>>(P, rois, roi_inds, roi_levels, order, A, out);
+    return check_launch("roi_align_3d_pyramid_forward (separable)");
+  }
+  const int64_t total = K * C * nout;         // one lane per output element: rows are in place whatever the order
+  k_roi_align3d_pyr_fwd<<<blocks_for(total, 256), 256, 0, as_stream(s)>>>(P, rois, roi_inds, roi_levels, C, total, out_w,
+                                                                          out_l, out_h, out);
+  return check_launch("roi_align_3d_pyramid_forward");
+}
+
+int inr_roi_align_3d_pyramid_backward(float* const* level_grads, const int32_t* level_dims, const float* level_scales,
+                                      int32_t n_levels, const float* rois, const int32_t* roi_inds,
+                                      const int32_t* roi_levels, const int32_t* order, int32_t N, int32_t C, int64_t K,
+                                      int32_t out_w, int32_t out_l, int32_t out_h, const float* grad_out, inr_stream_t s) {
+  PyrTable P;
+  const int rc = pyr_prepare(__func__, reinterpret_cast<const void* const*>(level_grads), level_dims, level_scales, n_levels,
+                             rois, roi_inds, roi_levels, grad_out, N, C, K, out_w, out_l, out_h, false, &P);
+  if (rc <= 0) return rc;
+  const int64_t nout = (int64_t)out_w * out_l * out_h;
+  int lds = 0, misfit = -1, wanted = 0;
+  for (int l = 0; l < n_levels && misfit < 0; ++l) {
+    PyrLevel& e = P.lv[l];
+    if (!e.ptr) continue;                      // no gradient for this level: its RoIs are skipped, its extents do not matter
+    ++wanted;
+    const bool ok = sep_grid_fits(C, K) && (int64_t)e.W * e.L * e.H < (1ll << 30);
+    const int b = ok ? sep_lds_bytes(e.W, e.L, e.H, out_w, out_l, out_h, true, &e.tmp_floats) : 0;
+    if (b <= 0) misfit = l;
+    lds = std::max(lds, b);
+  }
+  if (wanted == 0 && misfit < 0) return INR_OK;
+  if (g_roi_mode == 2 && misfit >= 0) {
+    set_error("%s: separable kernel: level %d does not fit it (tables within the LDS window, W*L*H < 2^30)", __func__, misfit);
+    return INR_EINVAL;
+  }
+  if (g_roi_mode != 1 && misfit < 0) {
+    SepArgs A;
+    A.C = C; A.W = 0; A.L = 0; A.H = 0; A.ow = out_w; A.ol = out_l; A.oh = out_h; A.scale = 0.0f;
+    A.cpb = sep_channels_per_block(C, K);
+    A.ngroups = (C + A.cpb - 1) / A.cpb;
+    A.K = (int)K;
+    A.tmp_floats = 0;
+    const unsigned grid = 8u * (unsigned)K * (unsigned)((A.ngroups + 7) / 8);
+    k_roi_align3d_sep_pyr_bwd<<<grid, SEP_THREADS, lds, as_stream(s)>>>(P, grad_out, rois, roi_inds, roi_levels, order, A);
+    return check_launch("roi_align_3d_pyramid_backward (separable)");
+  }
+  const int64_t total = K * C * nout;
+  k_roi_align3d_pyr_bwd<<<blocks_for(total, 256), 256, 0, as_stream(s)>>>(P, grad_out, rois, roi_inds, roi_levels, C, total,
+                                                                          out_w, out_l, out_h);
+  return check_launch("roi_align_3d_pyramid_backward");
 }
 
 // LDS of the channels-last backward: the backward's tables + the two slab intermediates for 16 channels (no staged gout)
