@@ -108,6 +108,7 @@ __device__ __forceinline__ f32x4 relu4(f32x4 v) {
 // for the whole kernel: the gather phase already holds 64 data + 12 fraction registers per lane and
 // must stay <= 128 VGPRs for 4 waves/SIMD.
 //   word 0 scale (f32)   1 byte offset of the level's first row   2 pa   3 pb   4 mask   5 hashed(0/1)
+//   word 6 all ones if hashed, else 0   7 all ones if dense, else 0   (the lane masks of index_terms below)
 // A level beyond num_levels needs no predicate: all its words are 0, so its gathers read row 0 of the
 // table (valid memory, finite) and its two features meet all-zero weight columns (the packer zero-fills
 // inputs >= 2 * num_levels).
@@ -131,7 +132,8 @@ __device__ __forceinline__ void stage_level_recs(const GridDesc& G, LevelRec* re
     r.a.w = !live ? 0u : (m ? 805459861u : s * s);
     r.b.x = !live ? 0u : (m ? m : 0xFFFFFFFFu);
     r.b.y = (live && m) ? 1u : 0u;
-    r.b.z = 0u; r.b.w = 0u;
+    r.b.z = (live && m) ? 0xFFFFFFFFu : 0u;
+    r.b.w = (live && !m) ? 0xFFFFFFFFu : 0u;
     recs[t] = r;
   }
 }
@@ -155,16 +157,25 @@ typedef unsigned int u32x2 __attribute__((__vector_size__(2 * sizeof(unsigned in
 // OPT-IN for inference, NeRFNetwork.half_table): a row is one dword, its byte offset half the fp32 one, and the two
 // features are widened when they are blended (v_cvt_f32_f16 x 2 per corner).  512 instead of 1024 algorithmic bytes
 // per sample; 32 instead of 16 rows per 128-byte line.
+// (two steps, so that a batch of gathers can form all its offsets first: see keep_offsets)
 template <bool kHalf = false>
-__device__ __forceinline__ u32x2 gather_row(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_off) {
+__device__ __forceinline__ uint32_t table_offset(uint32_t byte_off) {     // byte_off: of the fp32 table's row
+  return kHalf ? byte_off >> 1 : byte_off;
+}
+template <bool kHalf = false>
+__device__ __forceinline__ u32x2 gather_at(__amdgpu_buffer_rsrc_t rsrc, uint32_t off) {
   if constexpr (kHalf) {
     u32x2 r;
-    r[0] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)(byte_off >> 1), 0, 0);
+    r[0] = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)off, 0, 0);
     r[1] = 0u;
     return r;
   } else {
-    return __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)byte_off, 0, 0);
+    return __builtin_amdgcn_raw_buffer_load_b64(rsrc, (int)off, 0, 0);
   }
+}
+template <bool kHalf = false>
+__device__ __forceinline__ u32x2 gather_row(__amdgpu_buffer_rsrc_t rsrc, uint32_t byte_off) {
+  return gather_at<kHalf>(rsrc, table_offset<kHalf>(byte_off));
 }
 
 // Lane-paired gather for the FINE slots (levels 8..15).  Measured on MI355X (tools/micro/gather_bench.hip): the vector
@@ -186,7 +197,13 @@ __device__ __forceinline__ u32x2 gather_row(__amdgpu_buffer_rsrc_t rsrc, uint32_
 //  * weights and blending on the packed-fp32 pipe: the two features of a row arrive as a register pair and take the
 //    same weight (v_pk_fma_f32 with a broadcast operand), x-neighbour weights are formed two at a time (v_pk_mul_f32);
 //    every component is the same IEEE operation as before - (wx*wy)*wz, then fma in corner order - so nothing changes
-//    numerically.
+//    numerically;
+//  * the dense/hashed select of the coarse slots once per level instead of once per corner (index_terms), the colour
+//    sigmoid once on the lanes q < 3 instead of three times on the lanes q = 0 (rgb_channel_of_lane), and no clause
+//    breaker between back-to-back gathers (keep_offsets).  Hot loop of k_nerf_fwd<true,true> after these, read off the
+//    ISA (profiles/r07_issue_path_isa.md): xor-only gather block 210 VALU + 1 s_nop (was 235 + 18), blend + sigma net
+//    186 VALU / 18 MFMA, colour net 157 VALU / 42 MFMA, epilogue 20 VALU of which 2 transcendental (was 49 / 6),
+//    input loads 18: 591 VALU per tile (was 642 by the same reading).
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 struct Gathered {
@@ -215,6 +232,39 @@ __device__ __forceinline__ void wait_vmcnt() {
   if constexpr (N >= 0) __builtin_amdgcn_s_waitcnt((N & 0xF) | (0x7 << 4) | (0xF << 8) | ((N >> 4) << 14));
 }
 
+// Row index of a corner where the lanes of one instruction mix dense and hashed levels (the coarse slots; the fine slots
+// of a table with dense or dead fine levels).  The two modes differ in the combining operator only - c ^ (hy ^ hz)
+// against c + (hy + hz) - and used to be selected per CORNER (xor, add, v_cndmask each, after all four yz combinations
+// had been formed both ways).  Selected once per LEVEL instead: with the record's lane masks,
+//   X = hashed ? hy ^ hz : 0,   A = hashed ? 0 : hy + hz,   row = ((c ^ X) + A) & mask
+// is c ^ (hy ^ hz) in a hashed lane and c + (hy + hz) in a dense one - the same integer modulo 2^32, hence the same
+// address - at one v_bitop3 and an add/and per yz combination and a v_xad_u32 per corner.  A dead level (all-zero
+// record) gives row 0 as before.
+struct IndexTerms {
+  uint32_t x[4], a[4];      // yz combinations (y0z0, y1z0, y0z1, y1z1)
+  __device__ __forceinline__ uint32_t row(uint32_t c, int yz, uint32_t mask) const { return ((c ^ x[yz]) + a[yz]) & mask; }
+};
+__device__ __forceinline__ IndexTerms index_terms(uint32_t hy0, uint32_t hy1, uint32_t hz0, uint32_t hz1,
+                                                  uint32_t hashed_lanes, uint32_t dense_lanes) {
+  IndexTerms t;
+  t.x[0] = (hy0 ^ hz0) & hashed_lanes; t.x[1] = (hy1 ^ hz0) & hashed_lanes;
+  t.x[2] = (hy0 ^ hz1) & hashed_lanes; t.x[3] = (hy1 ^ hz1) & hashed_lanes;
+  t.a[0] = (hy0 + hz0) & dense_lanes; t.a[1] = (hy1 + hz0) & dense_lanes;
+  t.a[2] = (hy0 + hz1) & dense_lanes; t.a[3] = (hy1 + hz1) & dense_lanes;
+  return t;
+}
+
+// The offsets of a batch of gathers stay live until the batch is out.  A gather's address register dies at the load, so
+// the register allocator likes to hand it out again as (half of) the load's own destination.  gfx950 code objects are
+// built for XNACK "any", where a run of back-to-back memory instructions must be replayable: none of them may write a
+// register that one of them reads, so the compiler's hazard pass broke every such run with an `s_nop 0` - 18 per tile
+// between the gathers of the benchmark's kernel, 4 issue cycles each.  With the offsets read once more behind the batch
+// (an empty asm: no instruction) destinations and addresses are disjoint and the gathers go out back to back;
+// no scratch, and no more registers at the kernel's peak, which lies in the MLP.
+__device__ __forceinline__ void keep_offsets(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+  asm volatile("" : : "v"(a), "v"(b), "v"(c), "v"(d));
+}
+
 template <bool kFineHashed, bool kHalf = false, bool kPre = false>
 __device__ __forceinline__ void issue_gathers_impl(const LevelRec* __restrict__ my_recs, __amdgpu_buffer_rsrc_t rsrc,
                                                    float x0, float x1, float x2, Gathered& g) {
@@ -226,21 +276,21 @@ __device__ __forceinline__ void issue_gathers_impl(const LevelRec* __restrict__ 
     const uint4 ra = my_recs[li].a;
     const float s = __uint_as_float(ra.x);
     const uint32_t base = ra.y, pa = ra.z, pb = ra.w;
-    const uint32_t mask = my_recs[li].b.x;
+    const uint4 rb = my_recs[li].b;
+    const uint32_t mask = rb.x;
     const float px = x0 * s + 0.5f, py = x1 * s + 0.5f, pz = x2 * s + 0.5f;   // mul, add: not fused
     g.cfx[li] = __builtin_amdgcn_fractf(px); g.cfy[li] = __builtin_amdgcn_fractf(py); g.cfz[li] = __builtin_amdgcn_fractf(pz);
     const uint32_t cx = (uint32_t)px, cy = (uint32_t)py, cz = (uint32_t)pz;
     const uint32_t hy0 = cy * pa, hy1 = hy0 + pa;
     const uint32_t hz0 = cz * pb, hz1 = hz0 + pb;
-    const bool h = my_recs[li].b.y != 0;                 // per lane: the four q of a coarse slot mix dense and hashed
-    const uint32_t yz[4] = {h ? (hy0 ^ hz0) : (hy0 + hz0), h ? (hy1 ^ hz0) : (hy1 + hz0),
-                            h ? (hy0 ^ hz1) : (hy0 + hz1), h ? (hy1 ^ hz1) : (hy1 + hz1)};
+    const IndexTerms t = index_terms(hy0, hy1, hz0, hz1, rb.z, rb.w);   // per lane: the four q of a coarse slot mix dense and hashed
+    uint32_t off[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      const uint32_t c = cx + (k & 1);
-      const uint32_t idx = (h ? (c ^ yz[k >> 1]) : (c + yz[k >> 1])) & mask;
-      g.c[li][k] = gather_row<kHalf>(rsrc, base + idx * 8u);
-    }
+    for (int k = 0; k < 8; ++k) off[k] = table_offset<kHalf>(base + t.row(cx + (k & 1), k >> 1, mask) * 8u);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) g.c[li][k] = gather_at<kHalf>(rsrc, off[k]);
+    keep_offsets(off[0], off[1], off[2], off[3]);
+    keep_offsets(off[4], off[5], off[6], off[7]);
   }
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
@@ -248,7 +298,8 @@ __device__ __forceinline__ void issue_gathers_impl(const LevelRec* __restrict__ 
     const uint4 ra = rec->a;
     const float s = __uint_as_float(ra.x);
     const uint32_t base = ra.y, pa = ra.z, pb = ra.w;
-    const uint32_t mask = rec->b.x;
+    const uint4 rb = rec->b;
+    const uint32_t mask = rb.x;
     const float px = x0 * s + 0.5f, py = x1 * s + 0.5f, pz = x2 * s + 0.5f;
     const float fx = __builtin_amdgcn_fractf(px);
     g.fwx[i] = side ? fx : 1.0f - fx;
@@ -258,30 +309,31 @@ __device__ __forceinline__ void issue_gathers_impl(const LevelRec* __restrict__ 
     const uint32_t hz0 = cz * pb, hz1 = hz0 + pb;
     if (i == 0) wait_vmcnt<kWaitAfterCoarse>();
     else wait_vmcnt<kWaitBetweenFine>();
+    uint32_t off[4];           // byte offsets of the fp32 rows (y0z0, y1z0, y0z1, y1z1)
     if constexpr (kPre) {
       // sliced feed: the finest kSliceLevels levels (of pair 1's 12..15) arrive precomputed; its lanes ask for row 0 of
       // the table instead (all of them the SAME line: one look-up per instruction, no divergence) and the caller
       // overwrites those features
       const uint32_t keep = ((q >> 1) && i >= 4 - kSliceLevels) ? 0u : 0xFFFFFFFFu;
-      g.f[i][0] = gather_row<kHalf>(rsrc, (base + ((c ^ (hy0 ^ hz0)) & mask) * 8u) & keep);
-      g.f[i][1] = gather_row<kHalf>(rsrc, (base + ((c ^ (hy1 ^ hz0)) & mask) * 8u) & keep);
-      g.f[i][2] = gather_row<kHalf>(rsrc, (base + ((c ^ (hy0 ^ hz1)) & mask) * 8u) & keep);
-      g.f[i][3] = gather_row<kHalf>(rsrc, (base + ((c ^ (hy1 ^ hz1)) & mask) * 8u) & keep);
+      off[0] = (base + ((c ^ (hy0 ^ hz0)) & mask) * 8u) & keep;
+      off[1] = (base + ((c ^ (hy1 ^ hz0)) & mask) * 8u) & keep;
+      off[2] = (base + ((c ^ (hy0 ^ hz1)) & mask) * 8u) & keep;
+      off[3] = (base + ((c ^ (hy1 ^ hz1)) & mask) * 8u) & keep;
     } else if constexpr (kFineHashed) {       // every fine level of both pairs is hashed: xor-only index maths
-      g.f[i][0] = gather_row<kHalf>(rsrc, base + ((c ^ (hy0 ^ hz0)) & mask) * 8u);
-      g.f[i][1] = gather_row<kHalf>(rsrc, base + ((c ^ (hy1 ^ hz0)) & mask) * 8u);
-      g.f[i][2] = gather_row<kHalf>(rsrc, base + ((c ^ (hy0 ^ hz1)) & mask) * 8u);
-      g.f[i][3] = gather_row<kHalf>(rsrc, base + ((c ^ (hy1 ^ hz1)) & mask) * 8u);
+      off[0] = base + ((c ^ (hy0 ^ hz0)) & mask) * 8u;
+      off[1] = base + ((c ^ (hy1 ^ hz0)) & mask) * 8u;
+      off[2] = base + ((c ^ (hy0 ^ hz1)) & mask) * 8u;
+      off[3] = base + ((c ^ (hy1 ^ hz1)) & mask) * 8u;
     } else {
-      const bool h = rec->b.y != 0;
-      const uint32_t yz[4] = {h ? (hy0 ^ hz0) : (hy0 + hz0), h ? (hy1 ^ hz0) : (hy1 + hz0),
-                              h ? (hy0 ^ hz1) : (hy0 + hz1), h ? (hy1 ^ hz1) : (hy1 + hz1)};
+      const IndexTerms t = index_terms(hy0, hy1, hz0, hz1, rb.z, rb.w);
 #pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const uint32_t idx = (h ? (c ^ yz[k]) : (c + yz[k])) & mask;
-        g.f[i][k] = gather_row<kHalf>(rsrc, base + idx * 8u);
-      }
+      for (int k = 0; k < 4; ++k) off[k] = base + t.row(c, k, mask) * 8u;
     }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) off[k] = table_offset<kHalf>(off[k]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) g.f[i][k] = gather_at<kHalf>(rsrc, off[k]);
+    keep_offsets(off[0], off[1], off[2], off[3]);
   }
 }
 
@@ -518,6 +570,25 @@ __device__ __forceinline__ void mlp_layer(const float4* __restrict__ wsec, int l
     layer_bf<N_MT, N_G / 2>(reinterpret_cast<const uint4*>(wsec), lane, b, out);
   }
 #endif
+}
+
+// Colour epilogue.  The last layer leaves the three pre-activations of sample j in registers 0..2 of its lane q = 0
+// (rows 0..2 of D, both MFMA shapes).  Evaluating three sigmoids there costs three exp + three IEEE divisions - 49 VALU
+// instructions, 6 of them transcendental - on a quarter of the lanes, and the exec mask saves no issue slot.  Two
+// cross-row moves put channel c into lane q = c of the same sample instead:
+//   v_permlane16_swap vdst = o[0], src = o[1]:  row 1 of vdst <- row 0 of src   (rows: 16-lane groups = q)
+//   v_permlane32_swap vdst = that, src = o[2]:  rows 2, 3 of vdst <- rows 0, 1 of src
+// and the SAME expression runs once for all three channels; lane q < 3 then owns channel q.  Same operations on the
+// same values: the same bits.  (Lane q = 3 computes a value nobody reads.)
+__device__ __forceinline__ float rgb_channel_of_lane(const f32x4 o) {
+  const auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(o[0]), __float_as_uint(o[1]), false, false);
+  const unsigned a0 = a[0];
+  const auto b = __builtin_amdgcn_permlane32_swap(a0, __float_as_uint(o[2]), false, false);
+  const unsigned b0 = b[0];
+  return __uint_as_float(b0);
+}
+__device__ __forceinline__ float sigmoid_rgb(float o) {
+  return __frcp_rn(1.0f + __expf(-o));     // v_exp_f32 / v_rcp_f32: ~1e-7 relative
 }
 
 __device__ __forceinline__ float select4(int q, float a, float b, float c, float d) {
@@ -932,11 +1003,8 @@ __global__ void __launch_bounds__(kFieldThreads, kFieldMinWaves) k_nerf_fwd(cons
           }
         }
       }
-      if (valid && q == 0) {
-        rgb[m * 3 + 0] = __frcp_rn(1.0f + __expf(-o[0][0]));     // v_exp_f32 / v_rcp_f32: ~1e-7 relative
-        rgb[m * 3 + 1] = __frcp_rn(1.0f + __expf(-o[0][1]));
-        rgb[m * 3 + 2] = __frcp_rn(1.0f + __expf(-o[0][2]));
-      }
+      const float ch = sigmoid_rgb(rgb_channel_of_lane(o[0]));   // lane q < 3: channel q of sample j
+      if (valid && q < 3) rgb[m * 3 + q] = ch;
     }
   }
   INR_PROBE_EPILOGUE();
@@ -1102,7 +1170,7 @@ __global__ void __launch_bounds__(kFieldThreads, kFieldMinWaves) k_nerf_fwd_dirs
 #pragma unroll
     for (int t = 0; t < 4; ++t) h1[t] = relu4(h1[t]);
     mlp_layer<1, 4>(wl + kSig1 / 4, lane, h1, h2);
-    float r = 0.f, g = 0.f, b = 0.f;
+    float ch = 0.f;                                                     // lane q < 3: channel q, summed over the directions
     for (int d = 0; d < D; ++d) {                                       // wave-uniform trip count
       f32x4 cin[2], c1[4], c2[4], o[1];
       const float4 s4 = *reinterpret_cast<const float4*>(shl + d * 16 + q * 4);
@@ -1115,11 +1183,13 @@ __global__ void __launch_bounds__(kFieldThreads, kFieldMinWaves) k_nerf_fwd_dirs
 #pragma unroll
       for (int t = 0; t < 4; ++t) c2[t] = relu4(c2[t]);
       mlp_layer<1, 4>(wl + kCol2 / 4, lane, c2, o);
-      r += __frcp_rn(1.0f + __expf(-o[0][0]));
-      g += __frcp_rn(1.0f + __expf(-o[0][1]));
-      b += __frcp_rn(1.0f + __expf(-o[0][2]));
+      ch += sigmoid_rgb(rgb_channel_of_lane(o[0]));
     }
-    if (valid && q == 0) out[m] = make_float4(r * inv_d, g * inv_d, b * inv_d, fmaxf(h2[0][0], logit_min));
+    if (valid) {
+      float* o4 = reinterpret_cast<float*>(out + m);
+      if (q < 3) o4[q] = ch * inv_d;
+      if (q == 0) o4[3] = fmaxf(h2[0][0], logit_min);
+    }
   }
 }
 
