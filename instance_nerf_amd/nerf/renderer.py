@@ -51,6 +51,71 @@ def sample_pdf(bins, weights, n_samples, det=False):
     return bins_g[..., 0] + t * (bins_g[..., 1] - bins_g[..., 0])
 
 
+class MarchedHead:
+    """The prefetched head of a training render (``NeRFRenderer.march_ahead``): the ray/box test and the march of one
+    batch - and, with ``shade``, its frozen field and compositing forward - queued ahead of the render that consumes
+    them.  Every rule about whether it is still that render's head lives here."""
+    __slots__ = ("rays_o", "rays_d", "skip_labels", "n_rays", "grid_state", "nears", "fars", "xyzs", "dirs", "deltas",
+                 "rays", "counter", "shaded", "T_thresh", "density_scale", "slot_taken", "slot_index", "done", "side")
+
+    def __init__(self, rays_o, rays_d, skip_labels, n_rays, grid_state, nears=None, fars=None, xyzs=None, dirs=None,
+                 deltas=None, rays=None, counter=None, shaded=None, T_thresh=1e-4, density_scale=1.0, slot_taken=False,
+                 slot_index=-1, done=None, side=None):
+        self.rays_o, self.rays_d = rays_o, rays_d        # the caller's tensors, as handed to march_ahead
+        self.skip_labels = skip_labels                   # the label tensor the march was pruned with, or None
+        self.n_rays, self.grid_state = n_rays, grid_state        # ray count; iter_density of the grid marched through
+        self.nears, self.fars = nears, fars
+        self.xyzs, self.dirs, self.deltas, self.rays, self.counter = xyzs, dirs, deltas, rays, counter
+        # (weights_sum, depth, image, weights, sample_ray) of march_ahead(shade=True), for this T_thresh / density_scale
+        self.shaded, self.T_thresh, self.density_scale = shaded, float(T_thresh), float(density_scale)
+        self.slot_taken, self.slot_index = slot_taken, slot_index        # the renderer's step_counter slot (drop_ahead)
+        self.done, self.side = done, side                # event recorded behind the head on the stream it was queued on
+
+    def marched_for(self, rays_o, rays_d, skip_labels):
+        """Marched for THESE tensors (identity, not addresses: a freshly allocated batch may reuse the address of a freed
+        one - round-3 advisor) and, in the instance stage, pruned with THESE labels (round-5 advisor: a march that left
+        out the rays another mask tensor ignores would silently drop labelled rays of this batch)."""
+        return self.rays_o is rays_o and self.rays_d is rays_d and self.skip_labels is skip_labels
+
+    def fits(self, training, n_rays, grid_state):
+        """A training render of as many rays, through the occupancy grid the head was marched through."""
+        return bool(training) and self.n_rays == n_rays and self.grid_state == grid_state
+
+    def shaded_for(self, T_thresh, density_scale):
+        """The pre-shaded outputs, if they were computed with this threshold and density scale; None otherwise."""
+        if self.T_thresh == float(T_thresh) and self.density_scale == float(density_scale):
+            return self.shaded
+        return None
+
+    def wait(self):
+        """The current stream waits for the head (nothing to do on the stream it was queued on)."""
+        if self.done is None:
+            return
+        cur = torch.cuda.current_stream()
+        if self.side is not cur:
+            cur.wait_event(self.done)
+
+    def ordered_here(self, grid_state):
+        """The same buffers, already ordered on the consuming stream (nothing to wait for) and valid for the grid
+        generation given.  The slot flags stay with the original, which is the one a caller may drop."""
+        return MarchedHead(self.rays_o, self.rays_d, self.skip_labels, self.n_rays, grid_state, self.nears, self.fars,
+                           self.xyzs, self.dirs, self.deltas, self.rays, self.counter, self.shaded, self.T_thresh,
+                           self.density_scale)
+
+
+class _NoGate:
+    """``field_gate`` of a render that shares the device with no other view: nothing to order."""
+
+    def acquire(self):
+        pass
+
+    def release(self):
+        pass
+
+
+_NO_GATE = _NoGate()
+
+
 class NeRFRenderer(nn.Module):
     min_staged_batch = 1 << 20
 
@@ -112,6 +177,16 @@ class NeRFRenderer(nn.Module):
 
     def instance(self, x):
         return None
+
+    # optional: what the render paths ask a subclass before they take its fused kernels (``NeRFNetwork`` sets them)
+    num_instances = 0          # channels of the instance head; 0: none
+    _fusable = False           # the NeRF field has the fused kernels (forward_table, sh_table, nerf_render, _fused_nerf,
+    #                            _nerf_params, last_frame_path)
+    _fusable_inst = False      # ... and so has the instance field (instance_render, instance_head_train)
+
+    def instance_head_available(self, x):
+        """Field + K-channel compositing of the samples ``x`` as one autograd node (``instance_head_train``)."""
+        return False
 
     def reset_extra_state(self):
         if not self.cuda_ray:
@@ -185,7 +260,7 @@ class NeRFRenderer(nn.Module):
             bg_color = 1
         image = image + (1 - weights_sum).unsqueeze(-1) * bg_color
         results = {"image": image.view(*prefix, 3), "depth": depth.view(*prefix), "weights_sum": weights_sum.view(*prefix)}
-        if getattr(self, "num_instances", 0) > 0:
+        if self.num_instances > 0:
             logits = self.instance(xyzs.reshape(-1, 3)).view(N, T, -1)
             results["instance"] = torch.sum(weights.detach().unsqueeze(-1) * logits, dim=-2).view(*prefix, -1)
         return results
@@ -234,191 +309,222 @@ class NeRFRenderer(nn.Module):
         rays_o = rays_o.contiguous().view(-1, 3).float()
         rays_d = rays_d.contiguous().view(-1, 3).float()
         N = rays_o.shape[0]
-        device = rays_o.device
         aabb = self.aabb_train if self.training else self.aabb_infer
-        if marched is not None and not (self.training and marched["n_rays"] == N
-                                        and marched.get("grid_state", self.iter_density) == self.iter_density):
+        if marched is not None and not marched.fits(self.training, N, self.iter_density):
             self.drop_ahead(marched)         # other rays, or marched through an occupancy grid that has been updated since
             marched = None
         if marched is not None:
-            marched["consume"]()
-            nears, fars = marched["nears"], marched["fars"]
+            marched.wait()
+            nears, fars = marched.nears, marched.fars
         elif self.training and ce_prune and ce_labels is not None:
             nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, self.min_near, skip_labels=ce_labels,
                                                          ignore_index=ce_ignore_index)
         else:
             nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, aabb, self.min_near)
-        if bg_color is None:
-            bg_color = 1
-        results = {}
-        skipped_frac = None
-        with_instance = getattr(self, "num_instances", 0) > 0
         if not self.training and infer_mode == "auto":
             infer_mode = "fused_terminate" if self._recent_skippable() > self.terminate_above else "fused"
-
-        fused_inst = with_instance and getattr(self, "_fusable_inst", False) and hasattr(self, "instance_render")
-        if (not self.training and infer_mode == "fused_terminate" and getattr(self, "_fusable", False)
-                and (fused_inst or not with_instance)):
-            # ONE launch for field + compositing, with early termination per 16-ray group (opaque scenes)
-            counter = torch.zeros(2, dtype=torch.int32, device=device)
-            # both consumers take the writer's normalised coordinates and look the direction up per ray: the table
-            # feed (x01 + ray id, 24 instead of 32 bytes written per sample)
-            xyzs, _, deltas, rays = raymarching.march_rays_patch(
-                rays_o, rays_d, self.bound, self.density_bitfield, self.cascade, self.grid_size, nears, fars,
-                dt_gamma, max_steps, noises=noises if perturb else None, counter=counter, table=True)
-            if field_gate is not None:
-                field_gate.acquire()
-            weights_sum, depth, image, wbuf, evaluated = self.nerf_render(xyzs, deltas, rays, rays_d, T_thresh,
-                                                                          want_weights=with_instance, normalised=True)
-            if field_gate is not None:
-                field_gate.release()
-            if with_instance:
-                if field_gate is not None:       # a gather kernel too: never beside another view's field kernel
-                    field_gate.acquire()
-                results["instance"] = self.instance_render(xyzs, rays, wbuf, normalised=True).view(*prefix, -1)
-                if field_gate is not None:
-                    field_gate.release()
-            results["num_samples"] = counter
-            results["num_evaluated"] = evaluated
-            skipped_frac = (evaluated, int(xyzs.shape[0]), True)        # raw counter, marched total (host), "evaluated"
-        elif not self.training and infer_mode in ("fused", "fused_terminate"):
-            # full batch in four launches, patch-interleaved sample layout (csrc/raymarch.hip)
-            counter = torch.zeros(2, dtype=torch.int32, device=device)
-            # when the samples are consumed by the fused kernels only (NeRF field, fused instance render) the writer
-            # emits normalised coordinates + ray ids and the field reads a per-ray direction table (forward_table)
-            table = (fused_inst or not with_instance) and getattr(self, "_fusable", False) and hasattr(self, "forward_table")
-            # the direction table and the counter of the compositing kernel do not depend on the sample count: they
-            # are queued behind the count pass and run while the host waits for the count and prepares the write pass
-            early = {}
-
-            def while_waiting():
-                early["skippable"] = torch.zeros(1, dtype=torch.int64, device=device)
-                if table and hasattr(self, "sh_table"):
-                    early["shq"] = self.sh_table(rays_d)
-            xyzs, dirs, deltas, rays = raymarching.march_rays_patch(
-                rays_o, rays_d, self.bound, self.density_bitfield, self.cascade, self.grid_size, nears, fars,
-                dt_gamma, max_steps, noises=noises if perturb else None, counter=counter, table=table,
-                while_waiting=while_waiting)
-            if field_gate is not None:
-                field_gate.acquire()
-            sigmas, rgbs = self.forward_table(xyzs, dirs, rays_d, shq=early.get("shq")) if table else self(xyzs, dirs)
-            if field_gate is not None:
-                field_gate.release()
-            if self.density_scale != 1:
-                sigmas = self.density_scale * sigmas
-            skippable = early["skippable"]
-            if fused_inst:
-                # weights first, then the instance field accumulates w * logits on chip (no [M, K] round trip)
-                weights_sum, depth, image, wbuf = raymarching.composite_rays_patch(sigmas, rgbs, deltas, rays, T_thresh,
-                                                                                  return_weights=True, skippable=skippable)
-                if field_gate is not None:       # a gather kernel too: never beside another view's field kernel
-                    field_gate.acquire()
-                results["instance"] = self.instance_render(xyzs, rays, wbuf, normalised=table).view(*prefix, -1)
-                if field_gate is not None:
-                    field_gate.release()
-            else:
-                extra = self._instance_for_compositing(xyzs) if with_instance else None
-                out = raymarching.composite_rays_patch(sigmas, rgbs, deltas, rays, T_thresh, extra=extra,
-                                                       skippable=skippable)
-                weights_sum, depth, image = out[0], out[1], out[2]
-                if with_instance:
-                    results["instance"] = out[3][:, :self.num_instances].reshape(*prefix, -1)
-            results["num_samples"] = counter
-            if table:
-                results["frame_path"] = getattr(self, "last_frame_path", "fused")     # "fused" | "sliced" [+ " (probing)"]
-            skipped_frac = (skippable, int(xyzs.shape[0]), False)       # raw counter, marched total (host), "skippable"
-        elif self.training or infer_mode == "fused_raymajor":
-            if marched is not None:
-                counter = marched["counter"]
-                xyzs, dirs, deltas, rays = marched["xyzs"], marched["dirs"], marched["deltas"], marched["rays"]
-            else:
-                if self.training:
-                    counter = self.step_counter[self.local_step % 16]    # (total samples, N): written by the count pass
-                    self.local_step += 1
-                    mean_count = self.mean_count
-                else:
-                    counter = torch.zeros(2, dtype=torch.int32, device=device)
-                    mean_count = -1
-                    force_all_rays = True
-                xyzs, dirs, deltas, rays = raymarching.march_rays_train(
-                    rays_o, rays_d, self.bound, self.density_bitfield, self.cascade, self.grid_size, nears, fars,
-                    counter, mean_count, perturb, 128, force_all_rays, dt_gamma, max_steps, noises=noises)
-            if self.training:
-                self.last_counter = counter          # (total samples, N) of the march this render consumed
-            head = with_instance and getattr(self, "instance_head_available", lambda x: False)(xyzs)
-            shaded = None
-            if (marched is not None and marched.get("shaded") is not None and head and self.shade_ahead_applies()
-                    and marched["T_thresh"] == float(T_thresh) and marched["density_scale"] == float(self.density_scale)):
-                shaded = marched["shaded"]           # frozen field + compositing forward were queued with the march
-            else:
-                sigmas, rgbs = self(xyzs, dirs)
-                if self.density_scale != 1:
-                    sigmas = self.density_scale * sigmas
-            if head:
-                # the instance head as ONE autograd node (field + K-channel compositing; one backward launch)
-                weights_sum, depth, image, wbuf, sample_ray = shaded if shaded is not None else raymarching.composite_rays_train(
-                    sigmas, rgbs, deltas, rays, T_thresh, return_weights=True, total_dev=counter)
-                if ce_labels is not None:
-                    # the mask loss of the instance stage inside the compositing launch (Trainer.train_step passes the
-                    # batch's matched-mask ids): results["instance_ce"] = mean CE over the rows != ce_ignore_index
-                    inst, results["instance_ce"] = self.instance_head_train(
-                        xyzs, wbuf, sample_ray, rays, n_dev=counter, ce_labels=ce_labels.reshape(-1),
-                        ce_ignore_index=ce_ignore_index)
-                else:
-                    inst = self.instance_head_train(xyzs, wbuf, sample_ray, rays, n_dev=counter)
-                results["instance"] = inst[:, :self.num_instances].reshape(*prefix, -1)
-            else:
-                extra = self._instance_for_compositing(xyzs) if with_instance else None
-                out = raymarching.composite_rays_train(sigmas, rgbs, deltas, rays, T_thresh, extra=extra,
-                                                       total_dev=counter)
-                weights_sum, depth, image = out[0], out[1], out[2]
-                if with_instance:
-                    results["instance"] = out[3][:, :self.num_instances].reshape(*prefix, -1)
-            results["num_samples"] = counter
+        gate = _NO_GATE if field_gate is None else field_gate
+        jitter = noises if perturb else None
+        # the samples are consumed by the fused kernels only (NeRF field, fused instance render)
+        all_fused = self._fusable and (self._fusable_inst or self.num_instances == 0)
+        results = {}
+        if self.training or infer_mode == "fused_raymajor":
+            weights_sum, depth, image = self._render_ray_major(
+                results, prefix, rays_o, rays_d, nears, fars, marched, dt_gamma, max_steps, perturb, noises,
+                force_all_rays, T_thresh, ce_labels, ce_ignore_index)
+        elif infer_mode == "fused_terminate" and all_fused:
+            weights_sum, depth, image = self._render_terminating(
+                results, prefix, rays_o, rays_d, nears, fars, dt_gamma, max_steps, jitter, T_thresh, gate)
+        elif infer_mode in ("fused", "fused_terminate"):
+            weights_sum, depth, image = self._render_two_kernel(
+                results, prefix, rays_o, rays_d, nears, fars, dt_gamma, max_steps, jitter, T_thresh, gate, all_fused)
         elif infer_mode == "wavefront":
-            dtype = torch.float32
-            weights_sum = torch.zeros(N, dtype=dtype, device=device)
-            depth = torch.zeros(N, dtype=dtype, device=device)
-            image = torch.zeros(N, 3, dtype=dtype, device=device)
-            K = getattr(self, "num_instances", 0)
-            inst = torch.zeros(N, K, dtype=dtype, device=device) if with_instance else None
-            n_alive = N
-            rays_alive = torch.arange(n_alive, dtype=torch.int32, device=device)
-            rays_t = nears.clone()
-            step = 0
-            evaluated = 0
-            while step < max_steps and n_alive > 0:
-                n_step = max(min(N // n_alive, 8), 1)
-                xyzs, dirs, deltas = raymarching.march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d,
-                                                            self.bound, self.density_bitfield, self.cascade,
-                                                            self.grid_size, nears, fars, 128, perturb, dt_gamma,
-                                                            max_steps)
-                sigmas, rgbs = self(xyzs, dirs)
-                sigmas = self.density_scale * sigmas
-                extra = self.instance(xyzs) if with_instance else None
-                raymarching.composite_rays(n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum,
-                                           depth, image, T_thresh, extra=extra, extra_acc=inst)
-                evaluated += n_alive * n_step
-                rays_alive, n_alive = raymarching.compact_alive(rays_alive, n_alive)
-                step += n_step
-            if with_instance:
-                results["instance"] = inst.view(*prefix, -1)
+            weights_sum, depth, image = self._render_wavefront(
+                results, prefix, rays_o, rays_d, nears, fars, dt_gamma, max_steps, perturb, T_thresh)
         else:
             raise ValueError(f"unknown infer_mode {infer_mode!r}")
+        one_pass = not self.training and infer_mode != "wavefront"
+        return self._finish_rays(results, prefix, weights_sum, depth, image, nears, fars,
+                                 1 if bg_color is None else bg_color, mse_target, one_pass, jitter, dt_gamma, max_steps)
 
-        if not self.training and skipped_frac is not None:
-            self._note_skippable(*skipped_frac)
+    def _take_counter_slot(self):
+        """-> (index, row) of ``step_counter`` for the next training march - (total samples, N), written by its count
+        pass; ``local_step`` advances."""
+        index = self.local_step % 16
+        self.local_step += 1
+        return index, self.step_counter[index]
+
+    def _composite_with_logits(self, composite, results, prefix, xyzs, *args, **kwargs):
+        """K-channel compositing: ``composite(*args, extra=<logits of the samples>)`` -> weights_sum, depth, image; of the
+        rendered channels (``_instance_for_compositing``) the first ``num_instances`` are kept."""
+        with_instance = self.num_instances > 0
+        extra = self._instance_for_compositing(xyzs) if with_instance else None
+        out = composite(*args, extra=extra, **kwargs)
+        if with_instance:
+            results["instance"] = out[3][:, :self.num_instances].reshape(*prefix, -1)
+        return out[0], out[1], out[2]
+
+    def _render_terminating(self, results, prefix, rays_o, rays_d, nears, fars, dt_gamma, max_steps, jitter, T_thresh, gate):
+        """``fused_terminate``: ONE launch for field + compositing, with early termination per 16-ray group (opaque
+        scenes)."""
+        with_instance = self.num_instances > 0
+        counter = torch.zeros(2, dtype=torch.int32, device=rays_o.device)
+        # both consumers take the writer's normalised coordinates and look the direction up per ray: the table
+        # feed (x01 + ray id, 24 instead of 32 bytes written per sample)
+        xyzs, _, deltas, rays = raymarching.march_rays_patch(
+            rays_o, rays_d, self.bound, self.density_bitfield, self.cascade, self.grid_size, nears, fars,
+            dt_gamma, max_steps, noises=jitter, counter=counter, table=True)
+        gate.acquire()
+        weights_sum, depth, image, wbuf, evaluated = self.nerf_render(xyzs, deltas, rays, rays_d, T_thresh,
+                                                                      want_weights=with_instance, normalised=True)
+        gate.release()
+        if with_instance:
+            gate.acquire()                   # a gather kernel too: never beside another view's field kernel
+            results["instance"] = self.instance_render(xyzs, rays, wbuf, normalised=True).view(*prefix, -1)
+            gate.release()
+        results["num_samples"] = counter
+        results["num_evaluated"] = evaluated
+        self._note_skippable(evaluated, int(xyzs.shape[0]), True)        # raw counter, marched total (host), "evaluated"
+        return weights_sum, depth, image
+
+    def _render_two_kernel(self, results, prefix, rays_o, rays_d, nears, fars, dt_gamma, max_steps, jitter, T_thresh, gate,
+                           table):
+        """``fused``: the full batch in four launches, patch-interleaved sample layout (csrc/raymarch.hip).  ``table``:
+        the samples are consumed by the fused kernels only, so the writer emits normalised coordinates + ray ids and the
+        field reads a per-ray direction table (forward_table)."""
+        device = rays_o.device
+        fused_inst = self.num_instances > 0 and self._fusable_inst
+        counter = torch.zeros(2, dtype=torch.int32, device=device)
+        # the direction table and the counter of the compositing kernel do not depend on the sample count: they
+        # are queued behind the count pass and run while the host waits for the count and prepares the write pass
+        early = {}
+
+        def while_waiting():
+            early["skippable"] = torch.zeros(1, dtype=torch.int64, device=device)
+            if table:
+                early["shq"] = self.sh_table(rays_d)
+        xyzs, dirs, deltas, rays = raymarching.march_rays_patch(
+            rays_o, rays_d, self.bound, self.density_bitfield, self.cascade, self.grid_size, nears, fars,
+            dt_gamma, max_steps, noises=jitter, counter=counter, table=table, while_waiting=while_waiting)
+        gate.acquire()
+        sigmas, rgbs = self.forward_table(xyzs, dirs, rays_d, shq=early.get("shq")) if table else self(xyzs, dirs)
+        gate.release()
+        if self.density_scale != 1:
+            sigmas = self.density_scale * sigmas
+        skippable = early["skippable"]
+        if fused_inst:
+            # weights first, then the instance field accumulates w * logits on chip (no [M, K] round trip)
+            weights_sum, depth, image, wbuf = raymarching.composite_rays_patch(sigmas, rgbs, deltas, rays, T_thresh,
+                                                                              return_weights=True, skippable=skippable)
+            gate.acquire()                   # a gather kernel too: never beside another view's field kernel
+            results["instance"] = self.instance_render(xyzs, rays, wbuf, normalised=table).view(*prefix, -1)
+            gate.release()
+        else:
+            weights_sum, depth, image = self._composite_with_logits(
+                raymarching.composite_rays_patch, results, prefix, xyzs, sigmas, rgbs, deltas, rays, T_thresh,
+                skippable=skippable)
+        results["num_samples"] = counter
+        if table:
+            results["frame_path"] = self.last_frame_path     # "fused" | "sliced" [+ " (probing)"]
+        self._note_skippable(skippable, int(xyzs.shape[0]), False)       # raw counter, marched total (host), "skippable"
+        return weights_sum, depth, image
+
+    def _render_ray_major(self, results, prefix, rays_o, rays_d, nears, fars, marched, dt_gamma, max_steps, perturb, noises,
+                          force_all_rays, T_thresh, ce_labels, ce_ignore_index):
+        """Training, and ``fused_raymajor``: ray-major samples (taken from ``marched`` when there is one), field and
+        compositing as autograd nodes."""
+        with_instance = self.num_instances > 0
+        if marched is not None:
+            counter = marched.counter
+            xyzs, dirs, deltas, rays = marched.xyzs, marched.dirs, marched.deltas, marched.rays
+        else:
+            if self.training:
+                _, counter = self._take_counter_slot()
+                mean_count = self.mean_count
+            else:
+                counter = torch.zeros(2, dtype=torch.int32, device=rays_o.device)
+                mean_count = -1
+                force_all_rays = True
+            xyzs, dirs, deltas, rays = raymarching.march_rays_train(
+                rays_o, rays_d, self.bound, self.density_bitfield, self.cascade, self.grid_size, nears, fars,
+                counter, mean_count, perturb, 128, force_all_rays, dt_gamma, max_steps, noises=noises)
+        if self.training:
+            self.last_counter = counter          # (total samples, N) of the march this render consumed
+        head = with_instance and self.instance_head_available(xyzs)
+        shaded = marched.shaded_for(T_thresh, self.density_scale) if marched is not None else None
+        if shaded is not None and not (head and self.shade_ahead_applies()):
+            shaded = None
+        if shaded is None:                       # else: frozen field + compositing forward were queued with the march
+            sigmas, rgbs = self(xyzs, dirs)
+            if self.density_scale != 1:
+                sigmas = self.density_scale * sigmas
+        if head:
+            # the instance head as ONE autograd node (field + K-channel compositing; one backward launch)
+            weights_sum, depth, image, wbuf, sample_ray = shaded if shaded is not None else raymarching.composite_rays_train(
+                sigmas, rgbs, deltas, rays, T_thresh, return_weights=True, total_dev=counter)
+            if ce_labels is not None:
+                # the mask loss of the instance stage inside the compositing launch (Trainer.train_step passes the
+                # batch's matched-mask ids): results["instance_ce"] = mean CE over the rows != ce_ignore_index
+                inst, results["instance_ce"] = self.instance_head_train(
+                    xyzs, wbuf, sample_ray, rays, n_dev=counter, ce_labels=ce_labels.reshape(-1),
+                    ce_ignore_index=ce_ignore_index)
+            else:
+                inst = self.instance_head_train(xyzs, wbuf, sample_ray, rays, n_dev=counter)
+            results["instance"] = inst[:, :self.num_instances].reshape(*prefix, -1)
+        else:
+            weights_sum, depth, image = self._composite_with_logits(
+                raymarching.composite_rays_train, results, prefix, xyzs, sigmas, rgbs, deltas, rays, T_thresh,
+                total_dev=counter)
+        results["num_samples"] = counter
+        return weights_sum, depth, image
+
+    def _render_wavefront(self, results, prefix, rays_o, rays_d, nears, fars, dt_gamma, max_steps, perturb, T_thresh):
+        """``wavefront``: upstream's loop over the rays still alive, a few steps per pass."""
+        N, device = rays_o.shape[0], rays_o.device
+        with_instance = self.num_instances > 0
+        dtype = torch.float32
+        weights_sum = torch.zeros(N, dtype=dtype, device=device)
+        depth = torch.zeros(N, dtype=dtype, device=device)
+        image = torch.zeros(N, 3, dtype=dtype, device=device)
+        inst = torch.zeros(N, self.num_instances, dtype=dtype, device=device) if with_instance else None
+        n_alive = N
+        rays_alive = torch.arange(n_alive, dtype=torch.int32, device=device)
+        rays_t = nears.clone()
+        step = 0
+        while step < max_steps and n_alive > 0:
+            n_step = max(min(N // n_alive, 8), 1)
+            xyzs, dirs, deltas = raymarching.march_rays(n_alive, n_step, rays_alive, rays_t, rays_o, rays_d,
+                                                        self.bound, self.density_bitfield, self.cascade,
+                                                        self.grid_size, nears, fars, 128, perturb, dt_gamma,
+                                                        max_steps)
+            sigmas, rgbs = self(xyzs, dirs)
+            sigmas = self.density_scale * sigmas
+            extra = self.instance(xyzs) if with_instance else None
+            raymarching.composite_rays(n_alive, n_step, rays_alive, rays_t, sigmas, rgbs, deltas, weights_sum,
+                                       depth, image, T_thresh, extra=extra, extra_acc=inst)
+            rays_alive, n_alive = raymarching.compact_alive(rays_alive, n_alive)
+            step += n_step
+        if with_instance:
+            results["instance"] = inst.view(*prefix, -1)
+        return weights_sum, depth, image
+
+    def _finish_rays(self, results, prefix, weights_sum, depth, image, nears, fars, bg_color, mse_target, one_pass, jitter,
+                     dt_gamma, max_steps):
+        """Depth convention, background blend and (``mse_target``) the image loss -> ``results`` with image, depth and
+        weights_sum in the caller's shape.  ``one_pass``: the samples were composited by a one-pass inference mode;
+        ``jitter``: the per-ray noise their march started with, or None."""
+        N = weights_sum.shape[0]
         # Depth.  Upstream's training compositing counts t from the ray's first step, its inference compositing uses
         # the absolute ray parameter (SURVEY Appendix A.1 "Inference loop").  The one-pass inference modes composite
         # like the training kernel, so they add the start parameter back: sum w (t0 + t_rel) = depth + t0 * sum w.
         # (The wavefront mode runs upstream's loop and is absolute already.)
         t_start = None
-        if not self.training and infer_mode in ("fused", "fused_terminate", "fused_raymajor"):
+        if one_pass:
             t_start = nears
-            if perturb and noises is not None:
+            if jitter is not None:
                 dt_min = 2 * math.sqrt(3) / max_steps
                 dt_max = 2 * math.sqrt(3) * 2 ** (self.cascade - 1) / self.grid_size
-                t_start = nears + torch.clamp(nears * dt_gamma, dt_min, dt_max) * noises.to(nears)
+                t_start = nears + torch.clamp(nears * dt_gamma, dt_min, dt_max) * jitter.to(nears)
         bg3 = self._bg_triplet(bg_color)
         flows = torch.is_grad_enabled() and (image.requires_grad or weights_sum.requires_grad)
         bg_per_ray = torch.is_tensor(bg_color) and bg_color.is_cuda and bg_color.numel() == 3 * N
@@ -426,7 +532,7 @@ class NeRFRenderer(nn.Module):
                 and 0 < N <= raymarching.FINISH_MSE_MAX_RAYS and (bg3 is not None or bg_per_ray)):
             image, depth, results["image_mse"] = raymarching.finish_rays_mse(
                 image, weights_sum, depth, nears, fars, bg3 if bg3 is not None else bg_color, mse_target)
-        elif bg3 is not None and not (torch.is_grad_enabled() and (image.requires_grad or weights_sum.requires_grad)):
+        elif bg3 is not None and not flows:
             # no gradient flows through the shaded image (inference, or the instance stage on a frozen NeRF):
             # background blend + depth normalisation in one launch, in place on this call's own buffers
             lib = _lib.load()
@@ -534,8 +640,7 @@ class NeRFRenderer(nn.Module):
         """``march_ahead(shade=True)`` may also run the field and the compositing forward: a FROZEN NeRF on the fused
         kernel (nothing of it is trained, so neither launch depends on what the step in flight updates) rendered
         together with the one-node instance head."""
-        if not (getattr(self, "num_instances", 0) > 0 and getattr(self, "_fusable", False)
-                and hasattr(self, "_nerf_params") and hasattr(self, "instance_head_train")):
+        if not (self.num_instances > 0 and self._fusable and self._fusable_inst):
             return False
         if any(p.requires_grad for p in self._nerf_params()):
             return False
@@ -551,8 +656,8 @@ class NeRFRenderer(nn.Module):
         step's backward, whose table-gradient scatter leaves the CUs idle; measured: ~47 of its ~60 us hide), for a
         ``render(..., marched=<result>)`` of the SAME rays later.  Needs the steady state (``mean_count > 0``: no host
         read-back) and an occupancy grid that will not change in between (the caller's business: ``Trainer`` skips the
-        step before an occupancy update).  -> the dict ``run_cuda`` takes as ``marched`` or None (nothing queued,
-        nothing counted: the caller marches in the step as usual).
+        step before an occupancy update).  -> the ``MarchedHead`` ``run_cuda`` takes as ``marched``, or None
+        (nothing queued, nothing counted: the caller marches in the step as usual).
 
         shade (round 4): with a frozen NeRF under the one-node instance head (``shade_ahead_applies``) the field
         evaluation and the compositing forward do not depend on the trained parameters either: both are queued behind
@@ -582,7 +687,7 @@ class NeRFRenderer(nn.Module):
         # cost ~0.2 ms of host time per step - measured, profiles/r03_NOTES.txt 16).  Set A is read by step i (forward
         # and, through autograd's saved tensors, backward) while the side stream fills set B for step i + 1; set A is
         # written again for step i + 2 only after `side.wait_stream(main)` below, i.e. behind all of step i's launches.
-        M_al = (int(self.mean_count) + 127) // 128 * 128
+        M_al = raymarching.sample_capacity(self.mean_count)
         if bufs is not None:
             b = bufs
             if b["n_rays"] != N or b["n_samples"] < M_al or (shade and "sigmas" not in b):
@@ -597,10 +702,8 @@ class NeRFRenderer(nn.Module):
             self._ahead_turn ^= 1
         slot_taken = counter is None
         slot_index = -1
-        if counter is None:
-            slot_index = self.local_step % 16
-            counter = self.step_counter[slot_index]
-            self.local_step += 1
+        if slot_taken:
+            slot_index, counter = self._take_counter_slot()
         with torch.cuda.stream(side):
             nears, fars = raymarching.near_far_from_aabb(rays_o, rays_d, self.aabb_train, self.min_near,
                                                          out=(b["nears"], b["fars"]), skip_labels=skip_labels,
@@ -620,18 +723,8 @@ class NeRFRenderer(nn.Module):
             if side is not main:
                 done = torch.cuda.Event()
                 done.record(side)
-        out = {"n_rays": N, "key": (rays_o.data_ptr(), rays_d.data_ptr(), N), "rays_o": rays_o_in, "rays_d": rays_d_in,
-               "nears": nears, "fars": fars, "xyzs": xyzs, "dirs": dirs, "deltas": deltas, "rays": rays, "counter": counter,
-               "shaded": shaded, "T_thresh": float(T_thresh), "density_scale": float(self.density_scale),
-               "slot_taken": slot_taken, "slot_index": slot_index, "grid_state": self.iter_density,
-               "skip_labels": skip_labels}      # the label tensor the march was pruned with (identity-checked by the trainer)
-
-        def consume():
-            cur = torch.cuda.current_stream()
-            if done is not None and side is not cur:
-                cur.wait_event(done)
-        out["consume"] = consume
-        return out
+        return MarchedHead(rays_o_in, rays_d_in, skip_labels, N, self.iter_density, nears, fars, xyzs, dirs, deltas, rays,
+                           counter, shaded, T_thresh, self.density_scale, slot_taken, slot_index, done, side)
 
     def drop_ahead(self, marched):
         """A prefetched march that no render will consume: give its ``step_counter`` slot back (it would otherwise count
@@ -639,10 +732,10 @@ class NeRFRenderer(nn.Module):
         advisor: if another training render took a slot in between, stepping back would make the next render overwrite
         that real step's counter).  An orphaned slot further back is left alone: it holds the sample total of a real
         march of a real batch, a valid sample of what ``mean_count`` averages."""
-        if marched is not None and marched.get("slot_taken") and self.local_step > 0:
-            if marched.get("slot_index", -1) == (self.local_step - 1) % 16:
+        if marched is not None and marched.slot_taken and self.local_step > 0:
+            if marched.slot_index == (self.local_step - 1) % 16:
                 self.local_step -= 1
-            marched["slot_taken"] = False
+            marched.slot_taken = False
 
     @torch.no_grad()        # as upstream's: without it the NeRF stage's update ran the density query through the
     #                          composable autograd path (HIP encoder + BLAS layers, graph and all): 2.0 instead of 1.0 ms

@@ -949,12 +949,7 @@ class Trainer:
         ahead = self._ahead
         if ahead is not None:
             self._ahead = None
-            # the prefetch belongs to THESE tensors (identity, not addresses: a freshly allocated batch may reuse the
-            # address of a freed one - round-3 advisor)
-            # ... and, in the instance stage, was pruned with THESE labels (round-5 advisor: a march that left out the
-            # rays another mask tensor ignores would silently drop labelled rays of this batch)
-            if (ahead["rays_o"] is data["rays_o"] and ahead["rays_d"] is data["rays_d"]
-                    and ahead.get("skip_labels") is self._skip_labels(data)):
+            if ahead.marched_for(data["rays_o"], data["rays_d"], self._skip_labels(data)):
                 extra["marched"] = ahead            # this batch's march was queued under the previous step's backward
             elif hasattr(self.model, "drop_ahead"):
                 self.model.drop_ahead(ahead)        # never consumed: its step_counter slot is given back
@@ -1114,21 +1109,40 @@ class Trainer:
         return (self.model.mean_count, self.stage) + tuple((k, tuple(v.shape)) for k, v in sorted(data.items())
                                                             if torch.is_tensor(v))
 
+    def _prepare_capture(self, device):
+        """Moments, fixed-point gradient state and the hyper-parameter tensor must exist BEFORE a capture (an allocation
+        + zero fill inside it would be replayed every step)."""
+        from . import network as _network
+        opt = self.optimizer
+        for g in opt.param_groups:
+            for p in g["params"]:
+                if p.requires_grad:
+                    opt._moments(p)
+                    if getattr(p, "_is_hash_table", False):
+                        _network.fx_state(p)
+                        if _network.fx_bits() == 64:
+                            _network.fx_acc64(p)
+        opt.hyper_tensor(device)
+
+    def _replay_step(self, graph, written):
+        """Replays one captured step with the host bookkeeping around it.  ``written``: the counter the graph's march
+        wrote, copied to the renderer's ``step_counter`` slot of this step; None when the total is there already."""
+        m = self.model
+        self._lr_step()
+        self.optimizer.refresh_hyper()
+        graph.replay()
+        if written is not None:
+            m.step_counter[m.local_step % 16].copy_(written)
+        m.local_step += 1
+        self.optimizer.bump_versions()
+        if self.ema is not None:
+            self.ema.update()
+
     def _capture(self, data):
         m = self.model
         static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data.items()}
         slot = m.local_step % 16
-        opt = self.optimizer
-        for g in opt.param_groups:              # moments and the hyper-parameter tensor must exist BEFORE the capture
-            for p in g["params"]:               # (an allocation + zero fill inside it would be replayed every step)
-                if p.requires_grad:
-                    opt._moments(p)
-                    if getattr(p, "_is_hash_table", False):
-                        from . import network as _network
-                        _network.fx_state(p)        # the fixed-point gradient state of a table: not inside a capture either
-                        if _network.fx_bits() == 64:
-                            _network.fx_acc64(p)
-        opt.hyper_tensor(self.device)
+        self._prepare_capture(self.device)
         self.optimizer.zero_grad()
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
@@ -1142,16 +1156,8 @@ class Trainer:
     def _replay(self, data):
         G, m = self._graph, self.model
         copy_tensors([(G["static"][k], v) for k, v in data.items() if torch.is_tensor(v)])
-        self._lr_step()
-        self.optimizer.refresh_hyper()
-        G["graph"].replay()
-        cur = m.local_step % 16
-        if cur != G["slot"]:                    # the graph always writes the slot it was captured with
-            m.step_counter[cur].copy_(m.step_counter[G["slot"]])
-        m.local_step += 1
-        self.optimizer.bump_versions()
-        if self.ema is not None:
-            self.ema.update()
+        # the graph always writes the slot it was captured with
+        self._replay_step(G["graph"], m.step_counter[G["slot"]] if m.local_step % 16 != G["slot"] else None)
         return G["loss"].detach()
 
     # -- captured two-stream pipeline (use_graph and look_ahead) -------------------------------------------------
@@ -1189,30 +1195,19 @@ class Trainer:
         from .. import raymarching
         m, dev = self.model, data["rays_o"].device
         N = data["rays_o"].numel() // 3
-        M_al = (int(m.mean_count) + 127) // 128 * 128
+        M_al = raymarching.sample_capacity(m.mean_count)
         shade = self.stage == "instance" and self.shade_ahead and m.shade_ahead_applies()
         sets = []
         for _ in range(2):
             sets.append({"bufs": raymarching.march_train_buffers(N, M_al, dev, shade=shade),
                          "static": {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data.items()},
                          "counter": torch.zeros(2, dtype=torch.int32, device=dev), "marched": None})
-        opt = self.optimizer
-        for g in opt.param_groups:              # moments and the hyper-parameter tensor must exist BEFORE a capture
-            for p in g["params"]:
-                if p.requires_grad:
-                    opt._moments(p)
-                    if getattr(p, "_is_hash_table", False):
-                        from . import network as _network
-                        _network.fx_state(p)        # the fixed-point gradient state of a table: not inside a capture either
-                        if _network.fx_bits() == 64:
-                            _network.fx_acc64(p)
-        opt.hyper_tensor(dev)
+        self._prepare_capture(dev)
         self._pipe = {"key": self._graph_key(data), "sets": sets, "graphs": {}, "turn": 0, "primed": False,
                       "expect": None, "side": torch.cuda.Stream(device=dev)}
 
     def _pipe_capture(self, turn, prime, ahead):
         from . import network as _network
-        from .. import raymarching
         P, m = self._pipe, self.model
         S, Nx = P["sets"][turn], P["sets"][turn ^ 1]
         args = self._pipe_args()
@@ -1243,12 +1238,10 @@ class Trainer:
                                              counter=S["counter"], skip_labels=self._skip_labels(S["static"]), **args)
                 if S["marched"] is None:
                     raise RuntimeError("pipeline: march_ahead refused the batch (not the steady state / staged marcher)")
-            marched = dict(S["marched"])
-            marched["consume"] = lambda: None        # same graph or an earlier replay on the same stream: ordered already
-            # (the dict may come from an earlier capture; whether the buffers' CONTENT is current is _pipe_step's business
+            # same graph or an earlier replay on the same stream: ordered already
+            # (the head may come from an earlier capture; whether the buffers' CONTENT is current is _pipe_step's business
             # at every replay, so the renderer's own staleness check must not refuse it while the graph is captured)
-            marched["grid_state"] = getattr(m, "iter_density", 0)
-            self._ahead = marched
+            self._ahead = S["marched"].ordered_here(getattr(m, "iter_density", 0))
 
             def hook():
                 Nx["marched"] = m.march_ahead(Nx["static"]["rays_o"], Nx["static"]["rays_d"], stream=side, bufs=Nx["bufs"],
@@ -1295,16 +1288,8 @@ class Trainer:
             pairs.append((m.step_counter[m.local_step % 16], S["counter"]))
         G = P["graphs"].get((t, prime, ahead)) or self._pipe_capture(t, prime, ahead)
         copy_tensors(pairs)
-        self._lr_step()
-        self.optimizer.refresh_hyper()
-        G["graph"].replay()
-        if prime:
-            m.step_counter[m.local_step % 16].copy_(S["counter"])
-        m.local_step += 1
+        self._replay_step(G["graph"], S["counter"] if prime else None)
         m.last_counter = S["counter"]
-        self.optimizer.bump_versions()
-        if self.ema is not None:
-            self.ema.update()
         P["primed"], P["expect"] = ahead, (next_data["rays_o"] if ahead else None)
         P["grid_state"] = getattr(m, "iter_density", 0)
         P["turn"] = t ^ 1
@@ -1321,14 +1306,11 @@ class Trainer:
             return
         if self._side_stream is None:
             self._side_stream = torch.cuda.Stream(device=next_data["rays_o"].device)
-        kw = self._render_kwargs()
         ro, rd = next_data["rays_o"], next_data["rays_d"]
         if not (ro.is_contiguous() and rd.is_contiguous() and ro.dtype == torch.float32 and rd.dtype == torch.float32):
             return                                   # the buffers marched from must be the ones render() will see
-        self._ahead = m.march_ahead(ro, rd, dt_gamma=kw.get("dt_gamma", 0), perturb=True,
-                                    max_steps=kw.get("max_steps", 1024), stream=self._side_stream,
-                                    shade=self.stage == "instance" and self.shade_ahead, T_thresh=kw.get("T_thresh", 1e-4),
-                                    skip_labels=self._skip_labels(next_data))
+        self._ahead = m.march_ahead(ro, rd, stream=self._side_stream, skip_labels=self._skip_labels(next_data),
+                                    **self._pipe_args())
 
     def train_one_step(self, data, next_data=None):
         """One optimisation step on ``data``.  ``next_data`` (optional): the batch the NEXT call will get - its ray/box

@@ -124,6 +124,11 @@ def packbits(grid, thresh, bitfield=None):
     return bitfield
 
 
+def sample_capacity(mean_count):
+    """Samples a steady-state training march has room for: ``mean_count`` rounded up to the 128 of its alignment."""
+    return (int(mean_count) + 127) // 128 * 128
+
+
 def march_train_buffers(n_rays, n_samples, device, shade=False):
     """Persistent buffers for ``march_rays_train(..., out=)``: a caller that marches on a side stream every step
     (``NeRFRenderer.march_ahead``) must not allocate there - the caching allocator keeps one pool per stream, and blocks

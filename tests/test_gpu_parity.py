@@ -2466,7 +2466,7 @@ def test_dropping_a_prefetched_march_never_steps_over_a_later_slot(room):
     ro, rd = (_t(a)[None] for a in scene_rays(room, 512, seed=3))
     ro2, rd2 = (_t(a)[None] for a in scene_rays(room, 512, seed=4))
     a = net.march_ahead(ro, rd)
-    assert a is not None and a["slot_taken"] and a["slot_index"] == 0 and net.local_step == 1
+    assert a is not None and a.slot_taken and a.slot_index == 0 and net.local_step == 1
     net.drop_ahead(a)                                   # still the newest slot: handed back
     assert net.local_step == 0
     a = net.march_ahead(ro, rd)                         # slot 0 again
@@ -2475,10 +2475,48 @@ def test_dropping_a_prefetched_march_never_steps_over_a_later_slot(room):
     assert net.local_step == 2
     total_1 = int(net.step_counter[1, 0])
     net.drop_ahead(a)                                   # NOT the newest slot any more: nothing moves
-    assert net.local_step == 2 and not a["slot_taken"]
+    assert net.local_step == 2 and not a.slot_taken
     with torch.no_grad():
         net.render(ro, rd, bg_color=1, perturb=False)    # goes to slot 2
     assert net.local_step == 3 and int(net.step_counter[1, 0]) == total_1 > 0
+
+
+def test_a_stale_or_foreign_prefetched_head_is_dropped_and_the_render_marches_itself(room):
+    """``render(marched=)``: a fresh head changes nothing but the schedule; a head marched before the occupancy grid's
+    generation moved on, or for another batch, is dropped - its counter slot handed back - and the render marches for
+    itself: the same bits as without a head every time."""
+    from instance_nerf_amd.nerf import NeRFNetwork
+    net = NeRFNetwork(cuda_ray=True, num_instances=0, min_near=0.05).to(DEV).train()
+    net.density_bitfield.copy_(_t(room.density_bitfield(128, 1.0)))
+    net.mean_count = 60000
+    ro, rd = (_t(a)[None] for a in scene_rays(room, 512, seed=3))
+    ro2, rd2 = (_t(a)[None] for a in scene_rays(room, 256, seed=4))
+
+    def render(o, d, head=None):
+        with torch.no_grad():
+            out = net.render(o, d, bg_color=1, perturb=False, marched=head)
+        return [out[k].clone() for k in ("image", "depth", "weights_sum")] + [net.last_counter[0].clone()]
+
+    def same(x, y):
+        return all(torch.equal(a, b) for a, b in zip(x, y))
+    plain = render(ro, rd)
+    assert net.local_step == 1 and int(plain[3]) > 0
+    head = net.march_ahead(ro, rd)
+    assert head is not None and net.local_step == 2
+    assert same(render(ro, rd, head), plain) and net.local_step == 2 and net.last_counter is head.counter
+    # stale: the grid's generation moved on after the march
+    step0 = net.local_step
+    head = net.march_ahead(ro, rd)
+    net.iter_density += 1
+    assert same(render(ro, rd, head), plain)
+    # where a dropped head plus one render leaves it: the slot came back and the render's own march took it
+    assert net.local_step == step0 + 1 and not head.slot_taken
+    # wrong: the head of the 512 rays offered to a render of 256 others
+    plain2 = render(ro2, rd2)
+    step0 = net.local_step
+    head = net.march_ahead(ro, rd)
+    assert same(render(ro2, rd2, head), plain2)
+    assert net.local_step == step0 + 1 and not head.slot_taken
 
 
 def test_look_ahead_march_changes_nothing_but_the_schedule(room):
@@ -3043,7 +3081,7 @@ def test_shade_ahead_is_bit_identical_to_the_inline_head(room):
         if ahead:
             side = torch.cuda.Stream()
             marched = net.march_ahead(b["rays_o"], b["rays_d"], perturb=True, stream=side, shade=True)
-            assert marched is not None and marched["shaded"] is not None
+            assert marched is not None and marched.shaded is not None
             kw["marched"] = marched
         r = net.render(b["rays_o"], b["rays_d"], **kw)
         r["instance_ce"].backward()
