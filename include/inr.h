@@ -322,10 +322,17 @@ int inr_grid_encode_backward_levels(const float* x, const float* grad_out, const
  * training step - and integer sums do not depend on the order of arrival: the gradient becomes bit-reproducible.
  * fx_state: INR_GRID_FX_STATE_FLOATS device floats per table, zero-initialised by the caller once, then owned by these
  * three calls: [0,16) the scale of each level for the current step (a power of two; 0 = this level uses fp32 atomics),
- * [16,32) reference magnitudes, [32,48) the last step's largest |row gradient| per level, [48] fixed-point steps so far,
- * [49] near misses so far, [80,96) the largest fraction of the int32 range a row sum of each level has used so far, the
- * rest scratch.  A non-finite contribution to a fixed-point level (it has no int32
- * image) turns that level's WHOLE gradient into NaN in the finishing pass - as loud as the NaN rows fp32 atomics leave.
+ * [16,32) reference magnitudes, [32,48) the last step's largest |row gradient| per level, [48] steps so far in which at
+ * least one level (any level) ran on integer sums,
+ * [49] near misses so far, [80,96) the largest fraction of the integer range a row sum of each level has ended at so far
+ * (never above 1: a row that wrapped reads as a smaller value, a wrap cannot be observed here), the
+ * rest scratch.  GUARANTEE: every value the scatter adds to a row - the sum v of a run of equal rows inside one wave,
+ * possibly a single contribution - must have an integer image: |v x scale| < 2^31 (2^63 for int64 sums).  One that has
+ * none (out of range - the conversion would saturate -, v x scale beyond fp32, Inf, NaN) raises its level's flag and
+ * turns that level's WHOLE gradient into NaN in the finishing pass - as loud as the NaN rows fp32 atomics leave; the
+ * scale update then resets the level (scale 0, reference 0, flag cleared: fp32 atomics for one step).
+ * NOT detected: values that each fit but whose sum over one ROW, arriving from different waves, ends outside the
+ * range: that row wraps silently into a finite wrong gradient (sums that leave the range and come back are exact).
  * Per training step, on one stream:
  *   inr_grid_encode_backward_levels_fx   scatter of a level range; a level with a scale accumulates round(w g scale) as
  *                                        int32 bit patterns in grad_embeddings (zeroed by the caller), others fp32;
@@ -339,7 +346,8 @@ int inr_grid_encode_backward_levels(const float* x, const float* grad_out, const
  * with one extra scatter into a scratch buffer, so that no training step ever depends on the order of arrival) and
  * after an all-zero or non-finite gradient.  A near miss (a step that used more than 1/8 of the int32 range) is
  * counted; a row's FINAL sum that grows more than `headroom` times (128 in the product) against the reference - the
- * largest of the last ~50 steps - would wrap (intermediate overflow is harmless: int32 addition is modular); measured
+ * largest of the last ~50 steps - poisons its level when a single wave's run sum is that large and otherwise wraps
+ * unseen (see above; the wrapped row's maximum is arbitrary, so the next scale is not necessarily coarser); measured
  * peak use of the range over 3000 training steps: 0.06.  Quantisation: a row gradient is a multiple of headroom x
  * reference x 2^-30 (1.2e-7 of the level's recent largest at 128, ~5e-7 of a typical step's).
  * Why opt-in: a row whose gradient is below half a quantum gets none, and Adam with eps = 1e-15 (upstream's optimiser)

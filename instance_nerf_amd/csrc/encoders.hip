@@ -65,8 +65,12 @@ constexpr int kFxBase = 96;
 // tools/micro/atomic_type_bench.hip, profiles/r06_atomic_type_bench.txt) - and integer addition is associative, so the
 // table gradient no longer depends on the order in which the waves' requests arrive: training steps become
 // bit-reproducible.  scale == 0: the fp32 atomics of rounds 1-5.
-// A non-finite run sum cannot be represented (float -> int saturates, NaN becomes 0): it raises the level's flag instead
-// and the finishing pass turns the WHOLE level's gradient into NaN - as loud as the NaN rows fp32 atomics would leave.
+// A run sum whose image `v * scale` is not inside the integer's range - |v * scale| >= 2^31 (2^63 in the 64-bit form), a
+// product that leaves fp32, Inf, NaN - cannot be represented (float -> int SATURATES, NaN becomes 0): it raises the level's
+// flag instead and the finishing pass turns the WHOLE level's gradient into NaN - as loud as the NaN rows fp32 atomics
+// would leave.  What stays undetected: run sums that each fit but whose ROW sum, over several waves, ends outside the
+// range - that row wraps silently (modular addition; an INTERMEDIATE excursion past the range cancels, only the final
+// sum must fit).
 // Rounding is to nearest.  (A stochastic rounding with a deterministic draw - unbiased: contributions below the quantum
 // arrive in expectation - was built and measured in round 6: it injects +-1-quantum spikes into rows whose contributions
 // cancel, which Adam (eps 1e-15) turns into full steps: trained-scene PSNR 27.8 -> 26.6 dB.  Removed.)
@@ -91,14 +95,16 @@ __device__ __forceinline__ void run_reduce_atomic4(float* __restrict__ gemb, uin
   }
   const bool tail = (lane >= 60) || (next != key);
   if (scale > 0.0f) {
+    const float p = v * scale;                      // the run's sum in quanta: Inf when the product leaves fp32
     if (acc64) {
-      const long long q = __float2ll_rn(v * scale);
+      const long long q = __float2ll_rn(p);
       if (valid && tail && q != 0) atomicAdd(reinterpret_cast<unsigned long long*>(acc64) + addr, (unsigned long long)q);
     } else {
-      const int q = __float2int_rn(v * scale);
+      const int q = __float2int_rn(p);
       if (valid && tail && q != 0) atomicAdd(reinterpret_cast<int*>(gemb) + addr, q);
     }
-    if (valid && tail && !(fabsf(v) <= 3.402823466e+38f)) *bad_flag = 1.0f;      // (idempotent plain store)
+    // out of the integer's range (the conversion saturates), Inf or NaN: (idempotent plain store)
+    if (valid && tail && !(fabsf(p) < (acc64 ? 9223372036854775808.0f : 2147483648.0f))) *bad_flag = 1.0f;
   } else if (valid && tail && v != 0.0f) {
     atomicAdd(gemb + addr, v);
   }
@@ -148,9 +154,11 @@ __global__ void __launch_bounds__(256) k_grid_bwd(const float* __restrict__ x, c
 // ---- fixed-point table gradient: state, finishing pass, scale update ----------------------------------------------
 // State (device floats, INR_GRID_FX_STATE_FLOATS): [0,16) scale of each level for THIS step (a power of two; 0 = the level
 // is scattered with fp32 atomics), [16,32) reference magnitude (a slowly decaying maximum of the level's largest |row
-// gradient|), [32,48) this step's maximum, [48] steps with at least one fixed-point level, [49] near misses,
-// [64,80) "a non-finite contribution was seen" per level, [80,96) the largest fraction of the int32 range a row sum of
-// the level has used so far (1 = wrapped), [96 + 256 l + b] maximum seen by workgroup b of the finishing pass of level l.
+// gradient|), [32,48) this step's maximum, [48] steps with at least one fixed-point level (ANY level), [49] near misses,
+// [64,80) "a run sum without an integer image was seen" per level (out of range or non-finite), [80,96) the largest
+// fraction of the integer range a row sum of the level has ENDED at so far (at most 1 by construction: a row that wrapped
+// reads as some smaller value - a wrap is not observable here), [96 + 256 l + b] maximum seen by workgroup b of the
+// finishing pass of level l.
 
 // In place over the rows of levels [level0, level0 + gridDim.y): int32 sums -> fp32 gradients (levels with a scale), and
 // the level's largest |gradient| into the workgroup's slot (all levels: the fp32 levels need it to get a scale).
@@ -158,7 +166,7 @@ __global__ void __launch_bounds__(256) k_grid_grad_finish(float* __restrict__ ge
   __shared__ float red[4];
   const int l = level0 + blockIdx.y;
   const float scale = fx[l];
-  const bool poisoned = fx[kFxFlags + l] != 0.0f;                 // a non-finite contribution in a fixed-point level
+  const bool poisoned = fx[kFxFlags + l] != 0.0f;                 // a run sum of a fixed-point level had no integer image
   const float inv = scale > 0.0f ? 1.0f / scale : 0.0f;          // scale is a power of two: exact
   const size_t lo = (size_t)G.offsets[l] * 2, hi = (size_t)G.offsets[l + 1] * 2;       // floats; multiples of 16
   float4* p = reinterpret_cast<float4*>(gemb + lo);
@@ -230,11 +238,16 @@ __global__ void __launch_bounds__(256) k_grid_grad_finish64(long long* __restric
 // A level runs on fp32 atomics only while it has no reference (before the first step - the host primes it - and after an
 // all-zero or non-finite gradient).  A NEAR MISS - a step whose maximum used more than 1/8 of the range - is counted and
 // the peak use per level is kept ([80,96) of the state): the bench record reports both.  Only a row's FINAL sum must
-// fit: int32 addition is modular, intermediate overflow cancels.  Should a row ever wrap, its garbage maximum makes the
-// next scale coarser, never finer.
+// fit: integer addition is modular, an intermediate excursion past the range cancels (each single run sum must fit, though:
+// the conversion saturates, so one that does not poisons its level - run_reduce_atomic4).  A row whose in-range run sums
+// from different waves END outside the range wraps silently; its value is then anything inside the range, and nothing
+// here sees it: the next scale follows max(garbage, 0.97 reference) and may well be FINER than the true gradient needs.
 __global__ void __launch_bounds__(1024) k_grid_fx_update(float* __restrict__ fx, int num_levels, float headroom, float range) {
   // range = 2^31 (int32 sums) or 2^63 (int64 sums): `headroom x reference x scale <= range / 2`
   const int l = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  bool any_fx = false;                              // did ANY level run on integer sums this step?  (read before a wave
+  for (int i = 0; i < num_levels; ++i) any_fx |= fx[i] > 0.0f;      // of another level stores its new scale)
+  __syncthreads();
   if (l >= num_levels) return;
   float m = 0.0f;
   for (int b = lane; b < kFxBlocks; b += 64) m = fmaxf(m, fx[kFxBase + kFxBlocks * l + b]);
@@ -257,7 +270,7 @@ __global__ void __launch_bounds__(1024) k_grid_fx_update(float* __restrict__ fx,
   fx[kFxFlags + l] = 0.0f;
   if (old_scale > 0.0f && finite) fx[kFxPeak + l] = fmaxf(fx[kFxPeak + l], m * old_scale / range);
   if (near_miss) atomicAdd(fx + 49, 1.0f);
-  if (l == 0 && old_scale > 0.0f) fx[48] += 1.0f;
+  if (l == 0 && any_fx) fx[48] += 1.0f;
 }
 
 // Gradient with respect to the INPUT coordinates (upstream's dy_dx path, used when the positions require grad):

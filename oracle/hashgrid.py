@@ -153,19 +153,22 @@ def encode_input_grad(x, grad_out, embeddings, bound, table):
     return x.grad
 
 
-def fx_next_scale(old_ref, step_max, headroom=128.0):
-    """Scale rule of the fixed-point (int32) table-gradient scatter (include/inr.h ``inr_grid_fx_update``; no upstream
+def fx_next_scale(old_ref, step_max, headroom=128.0, sum_bits=32):
+    """Scale rule of the fixed-point table-gradient scatter (include/inr.h ``inr_grid_fx_update``; no upstream
     counterpart - upstream's ``grid_encode_backward`` sums with fp32 ``atomicAdd``): per level, from the largest |row
     gradient| of the step that has just finished and the running reference,
         ref'  = max(step_max, 0.97 * ref)         (0 when step_max is not finite)
         scale = 2 ** floor(log2(2**30 / (headroom * ref')))  clamped to 2**+-100      (0 when ref' == 0)
-    all in float32.  -> (scale, ref') as float32 arrays."""
+    all in float32; ``sum_bits`` = 64 (int64 sums) puts 2**62 in the place of 2**30.  -> (scale, ref') as float32 arrays."""
+    if sum_bits not in (32, 64):
+        raise ValueError("sum_bits must be 32 or 64")
     old_ref = np.asarray(old_ref, dtype=np.float32)
     m = np.asarray(step_max, dtype=np.float32)
     finite = np.isfinite(m)
     ref = np.where(finite, np.maximum(m, np.float32(0.97) * old_ref), np.float32(0)).astype(np.float32)
+    half_range = np.float32(2.0 ** (sum_bits - 2))
     with np.errstate(divide="ignore", over="ignore", invalid="ignore"):
-        e = np.floor(np.log2(np.float32(1073741824.0) / (np.float32(headroom) * ref).astype(np.float32)).astype(np.float32))
+        e = np.floor(np.log2(half_range / (np.float32(headroom) * ref).astype(np.float32)).astype(np.float32))
     e = np.clip(e, -100.0, 100.0)
     scale = np.where((ref > 0) & finite, np.exp2(e.astype(np.float64)), 0.0).astype(np.float32)
     return scale, ref
