@@ -1256,12 +1256,14 @@ __global__ void __launch_bounds__(kRayBlock) k_composite_train_fwd(const float* 
     const bool used = act && (T >= T_thresh || (base + lane) == 0);
     const float w = used ? alpha * T : 0.0f;
     const float t = t_carry + wave_incl_sum(dy, lane);
-    r += w * cr; g += w * cg; b += w * cb; ws += w; dsum += w * t;
+    // samples behind the termination point are not read upstream: whatever they hold (0 * NaN) must not reach the sums
+    if (used) { r += w * cr; g += w * cg; b += w * cb; ws += w; dsum += w * t; }
     if (wbuf && act) wbuf[i] = w;
     if (sample_ray && act) sample_ray[i] = rid;      // row of the ray's outputs (k_instance_head_bwd looks dL/dpix up by it)
     T_carry *= __shfl(P, 63, 64);
     t_carry = __shfl(t, 63, 64);
-    if (T_carry < T_thresh) {                        // wave-uniform: the rest of the ray is unused
+    if (!(T_carry >= T_thresh)) {                    // wave-uniform: the rest of the ray is unused (a NaN behind the
+                                                     // termination point of this chunk reaches the product: unused too)
       if (wbuf)
         for (int64_t k = (int64_t)base + 64 + lane; k < cnt; k += 64) {
           wbuf[(int64_t)off + k] = 0.0f;
@@ -1305,19 +1307,25 @@ __global__ void __launch_bounds__(kRayBlock) k_composite_train_extra_fwd(const f
       float e[8], w[8];
 #pragma unroll
       for (int u = 0; u < 8; ++u) { e[u] = extra[(i + u) * K + lane]; w[u] = wbuf[i + u]; }
+      // same order of additions as the scalar tail; a zero weight (behind the termination point) takes nothing from its
+      // row, whatever it holds (0 * NaN)
 #pragma unroll
-      for (int u = 0; u < 8; ++u) acc += w[u] * e[u];       // same order of additions as the scalar tail
+      for (int u = 0; u < 8; ++u) acc += w[u] != 0.0f ? w[u] * e[u] : 0.0f;
     }
     for (; s + 4 <= cnt; s += 4) {
       const int64_t i = (int64_t)off + s;
       const float e0 = extra[i * K + lane], e1 = extra[(i + 1) * K + lane], e2 = extra[(i + 2) * K + lane],
                   e3 = extra[(i + 3) * K + lane];
-      acc += wbuf[i] * e0;
-      acc += wbuf[i + 1] * e1;
-      acc += wbuf[i + 2] * e2;
-      acc += wbuf[i + 3] * e3;
+      const float w0 = wbuf[i], w1 = wbuf[i + 1], w2 = wbuf[i + 2], w3 = wbuf[i + 3];
+      acc += w0 != 0.0f ? w0 * e0 : 0.0f;
+      acc += w1 != 0.0f ? w1 * e1 : 0.0f;
+      acc += w2 != 0.0f ? w2 * e2 : 0.0f;
+      acc += w3 != 0.0f ? w3 * e3 : 0.0f;
     }
-    for (; s < cnt; ++s) acc += wbuf[(int64_t)off + s] * extra[((int64_t)off + s) * K + lane];
+    for (; s < cnt; ++s) {
+      const float w = wbuf[(int64_t)off + s];
+      acc += w != 0.0f ? w * extra[((int64_t)off + s) * K + lane] : 0.0f;
+    }
     extra_out[(int64_t)rid * K + lane] = acc;
   }
   if (ce.labels) {
@@ -1432,7 +1440,7 @@ __global__ void __launch_bounds__(kRayBlock) k_composite_train_bwd(
     }
     T_carry *= __shfl(P, 63, 64);
     cr_carry = __shfl(ar, 63, 64); cg_carry = __shfl(ag, 63, 64); cb_carry = __shfl(ab, 63, 64);
-    if (T_carry < T_thresh) dead = true;
+    if (!(T_carry >= T_thresh)) dead = true;          // NaN: a sample behind the termination point of this chunk
   }
 }
 

@@ -1400,12 +1400,20 @@ def test_generic_sampler_without_cuda_ray(params_k16, room, level_table):
 def test_composite_fuzz_against_the_c_oracle(rm, seed):
     """Random ray sets - empty rays, single-sample rays, rays that terminate early (large sigma), K = 0 / 16 / 64 extra
     channels, sample buffers smaller than the total (dropped rays) - training compositing forward against the scalar
-    C restatement, and the patch-interleaved inference compositing against the same numbers."""
+    C restatement, and the patch-interleaved inference compositing against the same numbers.  About one ray in twelve
+    has 130 .. 199 samples (a third 64-sample chunk; seeds 3 and 4 have such rays, up to 197 samples).  The patch layout is built
+    with tests/composite_reference.py::patch_slot_map (loops over the slot formula, nothing of raymarching.patch_slots);
+    there a whole 16-ray group is dropped when it does not fit, and its rays composite to nothing."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import composite_reference as cr
     from oracle import c_port
     rng = np.random.default_rng(700 + seed)
     N = int(rng.choice([1, 16, 33, 500]))
     cnt = rng.integers(0, 90, size=N).astype(np.int32)
     cnt[rng.random(N) < 0.15] = 0
+    long = rng.random(N) < 0.08
+    cnt[long] = rng.integers(130, 200, size=int(long.sum()))
     off = np.concatenate([[0], np.cumsum(cnt)[:-1]]).astype(np.int32)
     total = int(cnt.sum())
     rays = np.stack([rng.permutation(N).astype(np.int32), off, cnt], -1)
@@ -1424,6 +1432,20 @@ def test_composite_fuzz_against_the_c_oracle(rm, seed):
         assert np.abs(out[3].cpu().numpy() - ref["extra"]).max() < 2e-5
     if seed % 2 == 1 and cnt[-1] > 0:
         assert float(out[0][int(rays[-1, 0])]) == 0.0                          # the dropped ray composites to nothing
+    slots = cr.patch_slot_map(rays)
+    fits = ~cr.dropped_groups(rays, M)                                         # by row of rays; a ray of such a group fits
+    ids = rays[:, 0]                                                           # into the ray-major buffer too
+    lay = lambda a: _t(cr.to_patch(a[:total], slots, M))  # noqa: E731
+    pout = rm.composite_rays_patch(lay(sig), lay(rgb), lay(dl), _t(rays), 1e-4, extra=None if ex is None else lay(ex))
+    pout = [o.cpu().numpy() for o in pout]
+    assert np.abs(pout[0][ids[fits]] - ref["weights_sum"][ids[fits]]).max(initial=0) < 2e-6
+    assert np.abs(pout[1][ids[fits]] - ref["depth"][ids[fits]]).max(initial=0) < 1e-5
+    assert np.abs(pout[2][ids[fits]] - ref["image"][ids[fits]]).max(initial=0) < 2e-6
+    if K:
+        assert np.abs(pout[3][ids[fits]] - ref["extra"][ids[fits]]).max(initial=0) < 2e-5
+    for o in pout:
+        assert not o[ids[~fits]].any()                                         # dropped groups composite to nothing
+    assert (seed % 2 == 0 or total == 0) == bool(fits.all())
 
 
 def _fuzz_volume(rng, varied):
