@@ -225,6 +225,29 @@ int inr_composite_rays_patch_forward(const float* sigmas, const float* rgbs, con
                                      uint64_t* skippable /*device, nullable: += samples of steps at which a whole
                                      16-ray group is already below T_thresh - what inr_nerf_render would skip*/,
                                      inr_stream_t s);
+/* Records form of the two above (the frame path's 8-byte sample records): a sample is handed on as t [M] (float) and
+ * ray_ids [M] (int32), two separate arrays in the same patch-interleaved slots - same count pass, mask replay, re-march
+ * of rays past the capture row and rule for a group that does not fit; no position is formed, clamped or normalised.
+ * Position, dt and t - t_prev are functions of (ray, t): inr_nerf_forward_table_records rebuilds x01, and
+ * inr_composite_rays_patch_forward_records rebuilds (dt, t - t_prev) per ray from nears [N], noises [N] (nullable) and
+ * the step parameters of the march - dt = step(t), tn = t + dt, delta = tn - last_t, last_t = near + step(near) * noise
+ * at first and the previous sample's tn afterwards: the marcher's operations in its order, so every output has the bits
+ * of the positions form.  (Neither the bitfield nor the bound enters the step rule.)                                  */
+int inr_march_rays_patch_write_records(const float* rays_o, const float* rays_d, const uint8_t* bitfield,
+                                       float bound, float dt_gamma, int32_t max_steps, int64_t N,
+                                       int32_t cascade, int32_t H, int64_t M, const float* nears,
+                                       const float* fars, const float* noises /*nullable*/,
+                                       const int32_t* rays /*[N,3] from inr_march_rays_train_count*/,
+                                       float* t /*[M]*/, int32_t* ray_ids /*[M]*/, const void* workspace,
+                                       int32_t sample_cap, inr_stream_t s);
+int inr_composite_rays_patch_forward_records(const float* sigmas, const float* rgbs, const float* t /*[M]*/,
+                                             const int32_t* rays, int64_t N, int64_t M, float T_thresh,
+                                             const float* nears /*[N]*/, const float* noises /*[N] nullable*/,
+                                             float dt_gamma, int32_t max_steps, int32_t cascade, int32_t H,
+                                             const float* extra /*[M,K] nullable*/, int32_t K,
+                                             float* weights_sum, float* depth, float* image,
+                                             float* extra_out /*[N,K]*/, float* weights /*[M]*/,
+                                             uint64_t* skippable /*device, nullable*/, inr_stream_t s);
 /* No upstream counterpart in the submodule's extension; the counterpart of the reference pipeline's project_3d_masks step
  * (voxel masks of nerf_rcnn/run_rcnn.py:652-666 projected into the training images that
  * Mask2Former_sample/match_seg.py:99-102 reads).  For the samples of a patch-interleaved frame (inr_march_rays_patch_write)
@@ -421,6 +444,18 @@ int inr_nerf_forward_table(const float* x01, const int32_t* ray_ids, const float
                            float bound, const void* embeddings, const inr_grid_desc* desc /*host*/,
                            const float* packed /*device*/, float density_scale, float* sigma, float* rgb,
                            int32_t numerics, inr_stream_t s);
+/* Records feed of inr_nerf_forward_table (same results bit for bit, same numerics values, same launch shape): t [M] and
+ * ray_ids [M] from inr_march_rays_patch_write_records, and the per-ray rows of inr_ray_table_q - [N] rows of
+ * INR_RAY_TABLE_FLOATS floats, 16-byte aligned: the 16 values of inr_sh_table_q, then (o, 0) and (d, 0).  Every
+ * lane forms x01 = (clamp(o + t d, -bound, bound) + bound) * (1 / (2 bound)) with the marcher's own operations; the
+ * product equals the positions writer's division only where 2*bound is a power of two, and any other bound is refused
+ * (INR_EINVAL: take the positions feed).  8 instead of 16 bytes are read per sample.                               */
+#define INR_RAY_TABLE_FLOATS 24
+int inr_ray_table_q(const float* rays_o /*[N,3]*/, const float* rays_d /*[N,3]*/, int64_t N, float* out, inr_stream_t s);
+int inr_nerf_forward_table_records(const float* t, const int32_t* ray_ids, const float* ray_table_q, int64_t M,
+                             float bound, const void* embeddings, const inr_grid_desc* desc /*host*/,
+                             const float* packed /*device*/, float density_scale, float* sigma, float* rgb,
+                             int32_t numerics, inr_stream_t s);
 /* Sliced variant of inr_nerf_forward_table (round 5; same results bit for bit; fp32 table, 16 levels, hashed fine
  * levels): the three finest levels (13..15) are evaluated first, one level at a time over all samples - a hashed level
  * is 4 MiB, exactly one XCD's L2, and where those levels are finer than the spacing of a frame's samples nothing but a

@@ -18,6 +18,7 @@ MAX_LEVELS = 16
 GRID_FX_STATE_FLOATS = 4192      # include/inr.h INR_GRID_FX_STATE_FLOATS
 ROI_MAX_LEVELS = 8               # include/inr.h INR_ROI_MAX_LEVELS
 NUMERICS_TABLE_F16, NUMERICS_MLP_F16 = 1, 2      # include/inr.h INR_NUMERICS_*
+RAY_TABLE_FLOATS = 24            # include/inr.h INR_RAY_TABLE_FLOATS
 
 
 class GridDesc(Structure):
@@ -84,6 +85,12 @@ _SIGS = {
     "inr_nerf_forward_table_sliced_workspace_bytes": (c_int64, [c_int64]),
     "inr_nerf_forward_table_sliced": (c_int32, [P, P, P, c_int64, c_float, P, POINTER(GridDesc), P, c_float, P, P, P, P]),
     "inr_composite_rays_patch_forward": (c_int32, [P, P, P, P, c_int64, c_int64, c_float, P, c_int32, P, P, P, P, P, P, P]),
+    "inr_march_rays_patch_write_records": (c_int32, [P, P, P, c_float, c_float, c_int32, c_int64, c_int32, c_int32,
+                                                     c_int64, P, P, P, P, P, P, P, c_int32, P]),
+    "inr_composite_rays_patch_forward_records": (c_int32, [P, P, P, P, c_int64, c_int64, c_float, P, P, c_float, c_int32,
+                                                           c_int32, c_int32, P, c_int32, P, P, P, P, P, P, P]),
+    "inr_ray_table_q": (c_int32, [P, P, c_int64, P, P]),
+    "inr_nerf_forward_table_records": (c_int32, [P, P, P, c_int64, c_float, P, POINTER(GridDesc), P, c_float, P, P, c_int32, P]),
     "inr_project_masks_patch": (c_int32, [P, P, P, c_int64, c_int64, P, c_int32, c_int32, c_int32, P, c_int32, c_int32, c_int32,
                                           P, P]),
     "inr_march_rays": (c_int32, [c_int64, c_int32, P, P, P, P, c_float, c_float, c_int32, c_int32, c_int32,

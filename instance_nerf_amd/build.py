@@ -14,7 +14,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libinr_hip.so")
 SOURCES = ["raymarch.hip", "encoders.hip", "field_fused.hip", "roialign.hip", "mesh.hip", "components.hip", "match.hip",
            "overlap.hip", "detect.hip"]
-HEADERS = ["common.h", "grid_common.h", os.path.join("..", "..", "include", "inr.h")]
+HEADERS = ["common.h", "grid_common.h", "sample_pos.h", os.path.join("..", "..", "include", "inr.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function"]
 
@@ -22,7 +22,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=o
 # which files define which measured kernels: a committed profile belongs to these files only (an edit of the RoIAlign or the
 # marchers, or of a comment in include/inr.h, does not make a measurement of the field kernel stale)
 KERNEL_FILES = {
-    "field": ["field_fused.hip", "common.h", "grid_common.h"],        # k_nerf_fwd, k_instance_fwd, k_*_head_bwd, k_nerf_fwd_dirs
+    "field": ["field_fused.hip", "common.h", "grid_common.h", "sample_pos.h"],   # k_nerf_fwd, k_instance_fwd, k_*_head_bwd, k_nerf_fwd_dirs
     "scatter": ["encoders.hip", "common.h", "grid_common.h"],         # k_grid_bwd, k_adam_*
 }
 

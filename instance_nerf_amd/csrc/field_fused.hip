@@ -30,6 +30,7 @@
 
 #include "common.h"
 #include "grid_common.h"
+#include "sample_pos.h"
 
 namespace inr {
 
@@ -858,7 +859,14 @@ struct NerfSave {
 // kPre (table feed only; round 5, sliced frame path): the three FINEST levels (13..15, fine slots of lanes q = 2, 3) were
 // evaluated by k_grid_fine_slices; `d` (unused by the table feed) then points to their features, float2 [3][m_pad],
 // m_pad = M rounded up to 32; lanes q = 2, 3 read theirs from there and gather level 12 themselves.
-template <bool kColor, bool kTable = false, int kSave = 0, bool kHalf = false, bool kFast = false, bool kPre = false>
+// kRec (table feed only, not with kPre; records feed of the frame path): `x` is the [M] array of t of the records
+// writer and `shq` the per-ray rows of k_ray_table_q - kRayRowVec float4 per ray: the four SH rows, then the ray's
+// origin and direction.  A lane rebuilds its sample's x01 with the marcher's own operations (sample_pos.h; the host
+// admits power-of-two 2*bound only): 8 instead of 16 bytes read per sample, and the rows of a ray are shared by its
+// ~50 samples and the eight waves of a CU (L1 hits).  Everything behind the coordinates is the table feed's.
+constexpr int kRayRowVec = INR_RAY_TABLE_FLOATS / 4;
+template <bool kColor, bool kTable = false, int kSave = 0, bool kHalf = false, bool kFast = false, bool kPre = false,
+          bool kRec = false>
 __global__ void __launch_bounds__(kFieldThreads, kFieldMinWaves) k_nerf_fwd(const float* __restrict__ x, const float* __restrict__ d,
                                                                int64_t M, const int32_t* __restrict__ n_dev, float bound,
                                                                const float2* __restrict__ emb, uint32_t emb_bytes, GridDesc G,
@@ -901,7 +909,18 @@ __global__ void __launch_bounds__(kFieldThreads, kFieldMinWaves) k_nerf_fwd(cons
     const bool valid = m < n;
     TileIn me;
     f32x4 sh_in = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (kTable) {
+    if constexpr (kRec) {
+      static_assert(!kRec || (kTable && !kPre), "the records feed is a variant of the fused table feed");
+      const int64_t mm = valid ? m : n - 1;
+      const float t = x[mm];
+      const float4* row = shq + (int64_t)ray_ids[mm] * kRayRowVec;
+      const float4 t4 = row[q], o4 = row[4], d4 = row[5];
+      sh_in = f32x4{t4.x, t4.y, t4.z, t4.w};
+      const float rb_rcp = 1.0f / rb;        // exact: rb is a power of two
+      me.x0 = sample_x01_pow2(sample_pos(o4.x, t, d4.x, bound), bound, rb_rcp);
+      me.x1 = sample_x01_pow2(sample_pos(o4.y, t, d4.y, bound), bound, rb_rcp);
+      me.x2 = sample_x01_pow2(sample_pos(o4.z, t, d4.z, bound), bound, rb_rcp);
+    } else if constexpr (kTable) {
       const int64_t mm = valid ? m : n - 1;
       me.x0 = x[mm * 3 + 0]; me.x1 = x[mm * 3 + 1]; me.x2 = x[mm * 3 + 2];
       const float4 t4 = shq[(int64_t)ray_ids[mm] * 4 + q];
@@ -2802,6 +2821,48 @@ static void pack_section_as(int32_t numerics, float* dst, const float* W, int n_
   else pack_section(dst, W, n_out, n_in, n_mt, n_ks, kidx);
 }
 
+// The fused table launch behind inr_nerf_forward_table (kRec false: x = x01 [M,3], table = the SH rows) and
+// inr_nerf_forward_table_records (kRec true: x = t [M], table = the ray rows): one LDS request, priority, tile schedule and
+// cursor set for both - only where a tile's coordinates come from differs.
+template <bool kRec>
+static int forward_table_launch(const char* what, const float* x, const int32_t* ray_ids, const float* table, int64_t M,
+                                float bound, const void* embeddings, const inr_grid_desc* desc, const float* packed,
+                                float density_scale, float* sigma, float* rgb, int32_t numerics, inr_stream_t s) {
+  FieldTable t;
+  if (int rc = field_table(what, desc, embeddings, numerics & INR_NUMERICS_TABLE_F16, t)) return rc;
+  if (int rc = check_numerics(what, numerics, kAcceptAny)) return rc;
+  const size_t lds = std::max(kNerfFloats * sizeof(float) + kLevelRecBytes, (size_t)g_field_lds_min);
+  const int64_t n_tiles = (M + 15) / 16;
+  const hipStream_t st = as_stream(s);
+  HybridSchedule hybrid;         // frames (four rounds of eight 1024-tile chunks and more)
+  if (!hybrid.begin(st, n_tiles)) return INR_ELAUNCH;
+  with_flag(numerics & INR_NUMERICS_TABLE_F16, [&](auto half) {
+    with_mlp_f16(numerics & INR_NUMERICS_MLP_F16, [&](auto fast) {
+      launch_field(k_nerf_fwd<true, true, 0, decltype(half)::value, decltype(fast)::value, false, kRec>, lds, n_tiles, st,
+                   x, nullptr, M, nullptr, bound, t.emb, t.bytes, t.G, f4(packed), density_scale, sigma, rgb, nullptr,
+                   ray_ids, f4(table), NerfSave{}, hybrid.cursors());
+    });
+  });
+  hybrid.finish(st);
+  return check_launch(what + 4);       // without "inr_"
+}
+
+// per-ray rows of the records feed: out[n] = kRayRowVec float4 - the SH rows of k_sh_table_q (out[n][q][ks] =
+// sh[4*ks + q], the same sh4 on the same direction: the same bits), then (o, 0) and (d, 0)
+__global__ void __launch_bounds__(256) k_ray_table_q(const float* __restrict__ o, const float* __restrict__ d, int64_t N,
+                                                     float4* __restrict__ out) {
+  const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (n >= N) return;
+  const float dx = d[n * 3], dy = d[n * 3 + 1], dz = d[n * 3 + 2];
+  float v[16];
+  sh4(dx, dy, dz, v);
+  float4* row = out + n * kRayRowVec;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) row[q] = make_float4(v[q], v[4 + q], v[8 + q], v[12 + q]);
+  row[4] = make_float4(o[n * 3], o[n * 3 + 1], o[n * 3 + 2], 0.0f);
+  row[5] = make_float4(dx, dy, dz, 0.0f);
+}
+
 }  // namespace inr
 
 using namespace inr;
@@ -2878,23 +2939,30 @@ int inr_nerf_forward_table(const float* x01, const int32_t* ray_ids, const float
   INR_REQUIRE(x01 && ray_ids && sh_table_q && embeddings && packed && sigma && rgb, "null pointer");
   INR_REQUIRE(((uintptr_t)embeddings & 7) == 0 && ((uintptr_t)packed & 15) == 0 && ((uintptr_t)sh_table_q & 15) == 0,
               "embeddings/packed/sh_table_q misaligned");
-  FieldTable t;
-  if (int rc = field_table(__func__, desc, embeddings, numerics & INR_NUMERICS_TABLE_F16, t)) return rc;
-  if (int rc = check_numerics(__func__, numerics, kAcceptAny)) return rc;
-  const size_t lds = std::max(kNerfFloats * sizeof(float) + kLevelRecBytes, (size_t)g_field_lds_min);
-  const int64_t n_tiles = (M + 15) / 16;
-  const hipStream_t st = as_stream(s);
-  HybridSchedule hybrid;         // frames (four rounds of eight 1024-tile chunks and more)
-  if (!hybrid.begin(st, n_tiles)) return INR_ELAUNCH;
-  with_flag(numerics & INR_NUMERICS_TABLE_F16, [&](auto half) {
-    with_mlp_f16(numerics & INR_NUMERICS_MLP_F16, [&](auto fast) {
-      launch_field(k_nerf_fwd<true, true, 0, decltype(half)::value, decltype(fast)::value>, lds, n_tiles, st, x01,
-                   nullptr, M, nullptr, bound, t.emb, t.bytes, t.G, f4(packed), density_scale, sigma, rgb, nullptr,
-                   ray_ids, f4(sh_table_q), NerfSave{}, hybrid.cursors());
-    });
-  });
-  hybrid.finish(st);
-  return check_launch("nerf_forward_table");
+  return forward_table_launch<false>(__func__, x01, ray_ids, sh_table_q, M, bound, embeddings, desc, packed,
+                                     density_scale, sigma, rgb, numerics, s);
+}
+
+int inr_ray_table_q(const float* rays_o, const float* rays_d, int64_t N, float* out, inr_stream_t s) {
+  INR_REQUIRE(N >= 0, "bad sizes");
+  if (N == 0) return INR_OK;
+  INR_REQUIRE(rays_o && rays_d && out, "null pointer");
+  INR_REQUIRE(((uintptr_t)out & 15) == 0, "out misaligned");
+  k_ray_table_q<<<blocks_for(N, 256), 256, 0, as_stream(s)>>>(rays_o, rays_d, N, reinterpret_cast<float4*>(out));
+  return check_launch("ray_table_q");
+}
+
+int inr_nerf_forward_table_records(const float* t, const int32_t* ray_ids, const float* ray_table_q, int64_t M, float bound,
+                             const void* embeddings, const inr_grid_desc* desc, const float* packed, float density_scale,
+                             float* sigma, float* rgb, int32_t numerics, inr_stream_t s) {
+  INR_REQUIRE(records_bound_ok(bound), "the records feed needs a power-of-two 2*bound (take the positions feed)");
+  INR_REQUIRE(M >= 0 && desc, "bad argument");
+  if (M == 0) return INR_OK;
+  INR_REQUIRE(t && ray_ids && ray_table_q && embeddings && packed && sigma && rgb, "null pointer");
+  INR_REQUIRE(((uintptr_t)embeddings & 7) == 0 && ((uintptr_t)packed & 15) == 0 && ((uintptr_t)ray_table_q & 15) == 0,
+              "embeddings/packed/ray_table_q misaligned");
+  return forward_table_launch<true>(__func__, t, ray_ids, ray_table_q, M, bound, embeddings, desc, packed, density_scale,
+                                    sigma, rgb, numerics, s);
 }
 
 // ---- sliced frame path: level-major pre-pass over the three finest levels + fused kernel on the other thirteen ------

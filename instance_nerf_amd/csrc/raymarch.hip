@@ -5,6 +5,7 @@
 // written operation, no FMA), so sample positions, counts and offsets match the
 // CPU oracle exactly.  Integer/byte work here is HBM/latency bound - no MFMA.
 #include "common.h"
+#include "sample_pos.h"
 
 namespace inr {
 
@@ -309,9 +310,9 @@ __device__ __forceinline__ int march_ray(const MarchParams& P, const Ray& r, flo
   const StepRule<kConstDt> step(P);
   const float mb1 = fminf(ldexpf(1.0f, 0), P.bound), rmb1 = 1.0f / mb1;
   while (t < far && n < max_emit) {
-    const float px = clampf(r.ox + t * r.dx, -P.bound, P.bound);
-    const float py = clampf(r.oy + t * r.dy, -P.bound, P.bound);
-    const float pz = clampf(r.oz + t * r.dz, -P.bound, P.bound);
+    const float px = sample_pos(r.ox, t, r.dx, P.bound);
+    const float py = sample_pos(r.oy, t, r.dy, P.bound);
+    const float pz = sample_pos(r.oz, t, r.dz, P.bound);
     const float dt = step(P, t);
     int level = 0;
     float mb = mb1, rmb = rmb1;
@@ -509,9 +510,9 @@ __device__ __forceinline__ void replay_ray_t(const MarchParams& P, const Ray& r,
         const float dt = step(P, t);
         const float tn = t + dt;
         if (sub & (1u << j)) {
-          const float px = clampf(r.ox + t * r.dx, -P.bound, P.bound);
-          const float py = clampf(r.oy + t * r.dy, -P.bound, P.bound);
-          const float pz = clampf(r.oz + t * r.dz, -P.bound, P.bound);
+          const float px = sample_pos(r.ox, t, r.dx, P.bound);
+          const float py = sample_pos(r.oy, t, r.dy, P.bound);
+          const float pz = sample_pos(r.oz, t, r.dz, P.bound);
           emit(px, py, pz, dt, tn - last_t, t);
           last_t = tn;
           ++emitted;
@@ -598,9 +599,9 @@ __device__ __forceinline__ int march_ray_coop(const MarchParams& P, const Ray& r
       for (int j = 0; j < 63; ++j) c = j < lane ? c + step_dt(P, c) : c;
     }
     const bool in = c < far;
-    const float px = clampf(r.ox + c * r.dx, -P.bound, P.bound);
-    const float py = clampf(r.oy + c * r.dy, -P.bound, P.bound);
-    const float pz = clampf(r.oz + c * r.dz, -P.bound, P.bound);
+    const float px = sample_pos(r.ox, c, r.dx, P.bound);
+    const float py = sample_pos(r.oy, c, r.dy, P.bound);
+    const float pz = sample_pos(r.oz, c, r.dz, P.bound);
     const float dt = step_dt(P, c);
     const float tn = c + dt;
     int level = 0;
@@ -1515,6 +1516,10 @@ struct GroupCursor {
   }
 };
 
+// kRec (records form, inr_march_rays_patch_write_records): a sample is handed on as (t, ray) - `xyzs` is then the
+// [M] array of t, `ray_ids` its ray, dirs and deltas are not written.  Position, dt and t - t_prev are functions of
+// (ray, t): the field kernel and the compositing rebuild them with the marcher's operations (sample_pos.h, step_dt).
+template <bool kRec>
 __global__ void __launch_bounds__(kRayBlock) k_march_write_patch(MarchParams P, const float* __restrict__ rays_o,
                                                                  const float* __restrict__ rays_d, int64_t N, int64_t M,
                                                                  const float* __restrict__ nears,
@@ -1533,8 +1538,13 @@ __global__ void __launch_bounds__(kRayBlock) k_march_write_patch(MarchParams P, 
   if (cnt == 0 || (int64_t)cur.S + cur.total() > M) return;   // a group that does not fit is dropped whole
   const Ray r = load_ray(rays_o, rays_d, n);
   const float rb = 2.0f * P.bound;
-  auto emit = [&](float px, float py, float pz, float dt, float delta, float) {
+  auto emit = [&](float px, float py, float pz, float dt, float delta, float t) {
     const int64_t i = cur.next();
+    if constexpr (kRec) {
+      xyzs[i] = t;
+      ray_ids[i] = (int32_t)n;
+      return;
+    }
     if (normalise) {      // x01 = (p + bound) / (2 bound), the very operation the field kernel would do per lane
       px = (px + P.bound) / rb; py = (py + P.bound) / rb; pz = (pz + P.bound) / rb;
     }
@@ -1552,6 +1562,10 @@ __global__ void __launch_bounds__(kRayBlock) k_march_write_patch(MarchParams P, 
 }
 
 // one lane per ray; the 16 lanes of a group walk k in lockstep, so slot ranks come from one ballot
+// kRec (records form): `deltas` is the [M] array of t of k_march_write_patch<true>; (dt, t - t_prev) of a sample are
+// rebuilt with the marcher's operations in the marcher's order - dt = step_dt(t), tn = t + dt, delta = tn - last_t,
+// last_t = start_t(near, noise) of the ray at first and the previous sample's tn afterwards (march_ray's emit).
+template <bool kRec>
 __global__ void __launch_bounds__(kRayBlock) k_composite_patch_fwd(const float* __restrict__ sigmas,
                                                                    const float* __restrict__ rgbs,
                                                                    const float* __restrict__ deltas,
@@ -1559,7 +1573,9 @@ __global__ void __launch_bounds__(kRayBlock) k_composite_patch_fwd(const float* 
                                                                    float T_thresh, float* __restrict__ wbuf,
                                                                    float* __restrict__ weights_sum,
                                                                    float* __restrict__ depth, float* __restrict__ image,
-                                                                   unsigned long long* __restrict__ skippable) {
+                                                                   unsigned long long* __restrict__ skippable,
+                                                                   MarchParams P, const float* __restrict__ nears,
+                                                                   const float* __restrict__ noises) {
   const int64_t n = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int lane = threadIdx.x & 63, g0 = lane & ~(kGroup - 1), rr = lane & (kGroup - 1);
   const int32_t rid = n < N ? rays[n * 3] : 0;
@@ -1574,6 +1590,10 @@ __global__ void __launch_bounds__(kRayBlock) k_composite_patch_fwd(const float* 
 #pragma unroll
   for (int d = 1; d < 64; d <<= 1) maxc = max(maxc, __shfl_xor(maxc, d, 64));
   float T = 1.0f, r = 0, g = 0, b = 0, ws = 0, t = 0, dsum = 0;
+  float last_t = 0.0f;
+  if constexpr (kRec) {
+    if (n < N) last_t = start_t(P, nears[n], noises ? noises[n] : 0.0f);
+  }
   bool done = false;
   unsigned n_skip = 0;            // samples of steps at which every ray of the group is already below T_thresh
   // Eight steps per trip: the slots of steps k..k+7 depend on the counts only, so their 8 x 3 loads are requested
@@ -1593,7 +1613,8 @@ __global__ void __launch_bounds__(kRayBlock) k_composite_patch_fwd(const float* 
       slot[j] = (int64_t)S + __popc(field[j] & ((1u << rr) - 1u));
       S += __popc(field[j]);
       const int64_t i = (active[j] && !done) ? slot[j] : 0;      // a ray that is already opaque requests nothing new
-      dl[j] = reinterpret_cast<const float2*>(deltas)[i];
+      if constexpr (kRec) dl[j] = make_float2(deltas[i], 0.0f);       // t; (dt, delta) are formed below, in order
+      else dl[j] = reinterpret_cast<const float2*>(deltas)[i];
       sg[j] = sigmas[i];
       cr[j] = rgbs[i * 3]; cg[j] = rgbs[i * 3 + 1]; cb[j] = rgbs[i * 3 + 2];
     }
@@ -1604,6 +1625,11 @@ __global__ void __launch_bounds__(kRayBlock) k_composite_patch_fwd(const float* 
         if (rr == 0 && field[j] != 0 && live == 0) n_skip += __popc(field[j]);
       }
       if (active[j] && !done) {
+        if constexpr (kRec) {
+          const float dt = step_dt(P, dl[j].x), tn = dl[j].x + dt;
+          dl[j] = make_float2(dt, tn - last_t);
+          last_t = tn;
+        }
         const float alpha = 1.0f - expf(-sg[j] * dl[j].x);
         const float w = alpha * T;
         r += w * cr[j]; g += w * cg[j]; b += w * cb[j];
@@ -2053,10 +2079,27 @@ int inr_march_rays_patch_write(const float* rays_o, const float* rays_d, const u
   const MarchParams P = make_params(bitfield, bound, dt_gamma, max_steps, cascade, H);
   INR_REQUIRE(sample_cap == 0 || workspace, "sample_cap > 0 needs the workspace of the count pass");
   const uint32_t* mask = sample_cap > 0 ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const int32_t*>(workspace) + ws_ints(N)) : nullptr;
-  k_march_write_patch<<<blocks_for(N, kRayBlock), kRayBlock, march_lds_pad(), as_stream(s)>>>(P, rays_o, rays_d, N, M, nears, fars,
-                                                                                noises, rays, xyzs, dirs, deltas, mask,
-                                                                                cap_words_of(sample_cap), ray_ids, normalise);
+  k_march_write_patch<false><<<blocks_for(N, kRayBlock), kRayBlock, march_lds_pad(), as_stream(s)>>>(
+      P, rays_o, rays_d, N, M, nears, fars, noises, rays, xyzs, dirs, deltas, mask, cap_words_of(sample_cap), ray_ids,
+      normalise);
   return check_launch("march_rays_patch_write");
+}
+
+int inr_march_rays_patch_write_records(const float* rays_o, const float* rays_d, const uint8_t* bitfield, float bound,
+                                       float dt_gamma, int32_t max_steps, int64_t N, int32_t cascade, int32_t H,
+                                       int64_t M, const float* nears, const float* fars, const float* noises,
+                                       const int32_t* rays, float* t, int32_t* ray_ids, const void* workspace,
+                                       int32_t sample_cap, inr_stream_t s) {
+  INR_REQUIRE(rays_o && rays_d && bitfield && nears && fars && rays, "null pointer");
+  INR_REQUIRE(N > 0 && M >= 0, "bad sizes");
+  if (M == 0) return INR_OK;
+  INR_REQUIRE(t && ray_ids, "null output");
+  const MarchParams P = make_params(bitfield, bound, dt_gamma, max_steps, cascade, H);
+  INR_REQUIRE(sample_cap == 0 || workspace, "sample_cap > 0 needs the workspace of the count pass");
+  const uint32_t* mask = sample_cap > 0 ? reinterpret_cast<const uint32_t*>(reinterpret_cast<const int32_t*>(workspace) + ws_ints(N)) : nullptr;
+  k_march_write_patch<true><<<blocks_for(N, kRayBlock), kRayBlock, march_lds_pad(), as_stream(s)>>>(
+      P, rays_o, rays_d, N, M, nears, fars, noises, rays, t, nullptr, nullptr, mask, cap_words_of(sample_cap), ray_ids, 0);
+  return check_launch("march_rays_patch_write_records");
 }
 
 int inr_composite_rays_patch_forward(const float* sigmas, const float* rgbs, const float* deltas, const int32_t* rays,
@@ -2070,13 +2113,37 @@ int inr_composite_rays_patch_forward(const float* sigmas, const float* rgbs, con
   INR_REQUIRE(!extra || (extra_out && weights && K > 0 && K <= 64), "extra needs extra_out, weights and 0 < K <= 64");
   INR_REQUIRE(((uintptr_t)deltas & 7) == 0, "deltas must be 8-byte aligned");
   hipStream_t st = as_stream(s);
-  k_composite_patch_fwd<<<blocks_for(N, kRayBlock), kRayBlock, 0, st>>>(sigmas, rgbs, deltas, rays, N, M, T_thresh,
-                                                                        weights, weights_sum, depth, image,
-                                                                        reinterpret_cast<unsigned long long*>(skippable));
+  k_composite_patch_fwd<false><<<blocks_for(N, kRayBlock), kRayBlock, 0, st>>>(
+      sigmas, rgbs, deltas, rays, N, M, T_thresh, weights, weights_sum, depth, image,
+      reinterpret_cast<unsigned long long*>(skippable), MarchParams{}, nullptr, nullptr);
   if (extra_out && K > 0)     // also with no sample at all (M == 0, extra null): the rows of extra_out must be zeroed
     k_composite_patch_extra<<<blocks_for(N * 64, kRayBlock), kRayBlock, 0, st>>>(weights, extra, rays, N, M, K,
                                                                                  extra_out);
   return check_launch("composite_rays_patch_forward");
+}
+
+int inr_composite_rays_patch_forward_records(const float* sigmas, const float* rgbs, const float* t, const int32_t* rays,
+                                             int64_t N, int64_t M, float T_thresh, const float* nears,
+                                             const float* noises, float dt_gamma, int32_t max_steps, int32_t cascade,
+                                             int32_t H, const float* extra, int32_t K, float* weights_sum, float* depth,
+                                             float* image, float* extra_out, float* weights, uint64_t* skippable,
+                                             inr_stream_t s) {
+  INR_REQUIRE(N >= 0 && M >= 0, "bad sizes");
+  if (N == 0) return INR_OK;
+  INR_REQUIRE(rays && nears && weights_sum && depth && image, "null pointer");
+  INR_REQUIRE(M == 0 || (sigmas && rgbs && t), "null sample arrays");
+  INR_REQUIRE(max_steps > 0 && cascade > 0 && H > 0, "bad step parameters");
+  INR_REQUIRE(!extra || (extra_out && weights && K > 0 && K <= 64), "extra needs extra_out, weights and 0 < K <= 64");
+  hipStream_t st = as_stream(s);
+  // (the step rule needs neither the bitfield nor the bound)
+  const MarchParams P = make_params(nullptr, 0.0f, dt_gamma, max_steps, cascade, H);
+  k_composite_patch_fwd<true><<<blocks_for(N, kRayBlock), kRayBlock, 0, st>>>(
+      sigmas, rgbs, t, rays, N, M, T_thresh, weights, weights_sum, depth, image,
+      reinterpret_cast<unsigned long long*>(skippable), P, nears, noises);
+  if (extra_out && K > 0)
+    k_composite_patch_extra<<<blocks_for(N * 64, kRayBlock), kRayBlock, 0, st>>>(weights, extra, rays, N, M, K,
+                                                                                 extra_out);
+  return check_launch("composite_rays_patch_forward_records");
 }
 
 int inr_project_masks_patch(const float* xyzs, const float* weights, const int32_t* rays, int64_t N, int64_t M,

@@ -20,6 +20,7 @@ Execution paths, all HIP:
   encoders with the tiny MLP GEMMs left to rocBLAS through ``nn.Linear`` -
   upstream's default configuration (its ``--ff`` fused MLP is optional there too).
 """
+import math
 import os
 
 import torch
@@ -552,6 +553,10 @@ class NeRFNetwork(NeRFRenderer):
         self.frame_slices = __import__("os").environ.get("INR_FRAME_SLICES", "auto")
         self._slice_probe = None
         self.last_frame_path = "fused"         # what the last large frame ran on ("fused" | "sliced" [+ " (probing)"])
+        # Feed of the fused frame path: True = (t, ray id) records where they apply (``frame_feed``), False = positions
+        # always (x01 [M,3] + deltas [M,2]: the tests' twin, and before/after runs in one build).  Same outputs bit for bit.
+        self.frame_records = __import__("os").environ.get("INR_FRAME_RECORDS", "1") not in ("0", "off", "False", "false")
+        self.last_frame_feed = "positions"     # what the last ``fused`` frame was fed with ("records" | "positions")
 
     # ---- packed MFMA weights (cached until a weight tensor changes) ------------------------------
     def _packed_weights(self, which, numerics=0):
@@ -750,27 +755,79 @@ class NeRFNetwork(NeRFRenderer):
               "sh_table_q")
         return shq
 
-    def forward_table(self, x01, ray_ids, rays_d, shq=None):
+    @torch.no_grad()
+    def ray_table(self, rays_o, rays_d):
+        """Per-ray rows of the records feed of ``forward_table``: [N, 24] = the 16 values of ``sh_table``, (o, 0), (d, 0)."""
+        lib = _lib.load()
+        rays_o = rays_o.contiguous().float().view(-1, 3)
+        rays_d = rays_d.contiguous().float().view(-1, 3)
+        rows = torch.empty(rays_d.shape[0], _lib.RAY_TABLE_FLOATS, dtype=torch.float32, device=rays_d.device)
+        check(lib.inr_ray_table_q(ptr(rays_o, torch.float32, "rays_o"), ptr(rays_d, torch.float32, "rays_d"),
+                                  rays_d.shape[0], ptr(rows), stream_ptr()), "ray_table_q")
+        return rows
+
+    def records_apply(self):
+        """Whether a frame of this network may take the records feed at all: the switch is on, the fused kernel applies
+        and 2*bound is a power of two (the field kernel's product with the exact reciprocal then has the bits of the
+        positions writer's division; any other bound takes the positions feed)."""
+        return bool(self.frame_records and self._fusable and self.bound > 0
+                    and math.frexp(2.0 * float(self.bound))[0] == 0.5)
+
+    def _table_numerics(self):
+        if self.training:
+            return 0
+        # opt-in, the two halves of upstream's -O: the eval kernel gathers from a half-precision copy of the table
+        # (fp16 storage), and runs one fp16 MFMA pass per MLP GEMM instead of the fp32-class split
+        return ((_lib.NUMERICS_TABLE_F16 if self.half_table else 0) | (_lib.NUMERICS_MLP_F16 if self.mlp_fp16 else 0))
+
+    def plan_frame(self, M, records=False):
+        """The decisions of one frame of M samples, taken ONCE and before its write pass (``_use_slices`` counts its
+        calls while it probes): -> {"sliced", "feed"}.  ``forward_table(plan=)`` honours them rather than deciding again.
+        ``records``: the caller can consume the records feed; it is taken when the frame runs on the fused kernel,
+        neither sliced nor probing."""
+        numerics = self._table_numerics()
+        sliced = bool(not numerics and self._use_slices(M))
+        settled = bool(numerics) or self.last_frame_path == "fused"          # (the -O numerics never slice or probe)
+        feed = "records" if (records and self.records_apply() and not sliced and settled) else "positions"
+        return {"sliced": sliced, "feed": feed}
+
+    def forward_table(self, x01, ray_ids, rays_d, shq=None, rays_o=None, plan=None):
         """forward() for the fused frame path: x01 [M,3] normalised samples and ray_ids int32 [M] from
         ``march_rays_patch(table=True)``, rays_d [N,3].  The direction encoding is evaluated once per RAY into a
         table (``shq``: that table when the caller has already built it); results equal
-        ``forward(x, rays_d[ray_ids])``.  None when the fused kernel does not apply."""
+        ``forward(x, rays_d[ray_ids])``.  None when the fused kernel does not apply.
+
+        Records feed: the first argument is the [M] ``t`` of ``march_rays_patch(table="records")`` and ``rays_o`` [N,3]
+        is given (``shq``: the rows of ``ray_table`` when the caller has built them); same results bit for bit.
+        ``plan``: the frame's ``plan_frame`` result, when the caller has taken it already."""
         if not self._fusable:
             return None
         lib = _lib.load()
         M = x01.shape[0]
         dev = x01.device
+        records = x01.dim() == 1
+        if records:
+            if rays_o is None or not self.records_apply():
+                raise ValueError("forward_table: the records feed needs rays_o, a power-of-two 2*bound and frame_records")
+            if plan is not None and plan["feed"] != "records":
+                raise ValueError("forward_table: this frame was planned on the positions feed")
+        if plan is None:
+            plan = {"sliced": False, "feed": "records"} if records else self.plan_frame(M)
         if shq is None:
-            shq = self.sh_table(rays_d)
+            shq = self.ray_table(rays_o, rays_d) if records else self.sh_table(rays_d)
         sigma = torch.empty(M, dtype=torch.float32, device=dev)
         rgb = torch.empty(M, 3, dtype=torch.float32, device=dev)
-        numerics = 0
-        if not self.training:
-            # opt-in, the two halves of upstream's -O: the eval kernel gathers from a half-precision copy of the table
-            # (fp16 storage), and runs one fp16 MFMA pass per MLP GEMM instead of the fp32-class split
-            numerics = ((_lib.NUMERICS_TABLE_F16 if self.half_table else 0)
-                        | (_lib.NUMERICS_MLP_F16 if self.mlp_fp16 else 0))
-        if not numerics and self._use_slices(M):
+        numerics = self._table_numerics()
+        self.last_frame_feed = plan["feed"]
+        if records:
+            check(lib.inr_nerf_forward_table_records(ptr(x01, torch.float32, "t", allow_none=M == 0),
+                                               ptr(ray_ids, torch.int32, "ray_ids", allow_none=M == 0), ptr(shq), M,
+                                               float(self.bound), self._table_ptr(self.encoder, numerics),
+                                               self.encoder.desc, ptr(self._packed_weights("nerf", numerics)), 1.0,
+                                               ptr(sigma, allow_none=M == 0), ptr(rgb, allow_none=M == 0), numerics,
+                                               stream_ptr()), "nerf_forward_table_records")
+            return sigma, rgb
+        if plan["sliced"]:
             # sliced frame path (round 5): the three finest levels by a level-major pre-pass (every XCD's L2 then holds
             # the one level the chip is working on), the fused kernel on the other thirteen; same numbers bit for bit
             need = lib.inr_nerf_forward_table_sliced_workspace_bytes(M) // 4

@@ -391,23 +391,46 @@ class NeRFRenderer(nn.Module):
                            table):
         """``fused``: the full batch in four launches, patch-interleaved sample layout (csrc/raymarch.hip).  ``table``:
         the samples are consumed by the fused kernels only, so the writer emits normalised coordinates + ray ids and the
-        field reads a per-ray direction table (forward_table)."""
+        field reads a per-ray direction table (forward_table).
+
+        Feed of a ``table`` frame: (t, ray id) records - 8 bytes per sample between march, field and compositing, which
+        rebuild position and (dt, t - t_prev) with the marcher's operations - when nothing else reads positions
+        (``num_instances == 0``), 2*bound is a power of two and the field runs on the fused kernel, neither sliced nor
+        probing (``plan_frame``, asked once the sample count is known, before the write pass); positions (x01 [M,3] +
+        deltas [M,2]) otherwise and under ``frame_records = False``.  Same outputs bit for bit; ``results["frame_feed"]``."""
         device = rays_o.device
         fused_inst = self.num_instances > 0 and self._fusable_inst
         counter = torch.zeros(2, dtype=torch.int32, device=device)
+        may_record = bool(table and self.num_instances == 0 and self.records_apply())
         # the direction table and the counter of the compositing kernel do not depend on the sample count: they
         # are queued behind the count pass and run while the host waits for the count and prepares the write pass
         early = {}
 
         def while_waiting():
             early["skippable"] = torch.zeros(1, dtype=torch.int64, device=device)
-            if table:
+            if may_record:
+                early["rows"] = self.ray_table(rays_o, rays_d)
+            elif table:
                 early["shq"] = self.sh_table(rays_d)
+
+        def feed_of(M):
+            early["plan"] = self.plan_frame(M, records=may_record)
+            return raymarching.RECORDS if early["plan"]["feed"] == "records" else True
         xyzs, dirs, deltas, rays = raymarching.march_rays_patch(
             rays_o, rays_d, self.bound, self.density_bitfield, self.cascade, self.grid_size, nears, fars,
-            dt_gamma, max_steps, noises=jitter, counter=counter, table=table, while_waiting=while_waiting)
+            dt_gamma, max_steps, noises=jitter, counter=counter, table=feed_of if table else False,
+            while_waiting=while_waiting)
+        records = None
         gate.acquire()
-        sigmas, rgbs = self.forward_table(xyzs, dirs, rays_d, shq=early.get("shq")) if table else self(xyzs, dirs)
+        if not table:
+            sigmas, rgbs = self(xyzs, dirs)
+        elif early["plan"]["feed"] == "records":
+            # xyzs is t [M]; the compositing rebuilds (dt, t - t_prev) from it and the rays' start
+            records = raymarching.MarchRecords(nears, jitter, dt_gamma, max_steps, self.cascade, self.grid_size)
+            sigmas, rgbs = self.forward_table(xyzs, dirs, rays_d, shq=early["rows"], rays_o=rays_o, plan=early["plan"])
+            deltas = xyzs
+        else:       # (a frame that could have recorded but is sliced or probing: the [N,16] table is built here)
+            sigmas, rgbs = self.forward_table(xyzs, dirs, rays_d, shq=early.get("shq"), plan=early["plan"])
         gate.release()
         if self.density_scale != 1:
             sigmas = self.density_scale * sigmas
@@ -422,10 +445,11 @@ class NeRFRenderer(nn.Module):
         else:
             weights_sum, depth, image = self._composite_with_logits(
                 raymarching.composite_rays_patch, results, prefix, xyzs, sigmas, rgbs, deltas, rays, T_thresh,
-                skippable=skippable)
+                skippable=skippable, **({"records": records} if records is not None else {}))
         results["num_samples"] = counter
         if table:
             results["frame_path"] = self.last_frame_path     # "fused" | "sliced" [+ " (probing)"]
+            results["frame_feed"] = early["plan"]["feed"]    # "records" | "positions"
         self._note_skippable(skippable, int(xyzs.shape[0]), False)       # raw counter, marched total (host), "skippable"
         return weights_sum, depth, image
 

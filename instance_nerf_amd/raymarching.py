@@ -216,6 +216,8 @@ def march_rays_train(rays_o, rays_d, bound, density_bitfield, C, H, nears, fars,
     return xyzs, dirs, deltas, rays
 
 
+RECORDS = "records"   # march_rays_patch(table=RECORDS): the (t, ray id) feed of the frame path
+
 GROUP = 16   # rays per group of the patch-interleaved layout (csrc/raymarch.hip::kGroup)
 
 
@@ -250,6 +252,10 @@ def march_rays_patch(rays_o, rays_d, bound, density_bitfield, C, H, nears, fars,
 
     ``table=True`` is the feed of ``NeRFNetwork.forward_table``: xyzs come back NORMALISED,
     (p + bound) / (2 bound), and the second result is the int32 ray id of every sample instead of its direction.
+    ``table="records"`` is the records feed (``forward_table(t, ray_ids, rays_d, rays_o=...)`` and
+    ``composite_rays_patch(..., records=...)``): -> (t [M], ray_ids int32 [M], None, rays) - the ray parameter of every
+    sample and its ray, in the same slots; position, dt and t - t_prev are rebuilt by the consumers, bit for bit.
+    ``table`` may also be a callable: it is called with M once the count is known and returns one of the values above.
     ``while_waiting``: called once the count pass and the read-back of M are queued (see ``_read_count``).
     """
     lib = _lib.load()
@@ -270,6 +276,16 @@ def march_rays_patch(rays_o, rays_d, bound, density_bitfield, C, H, nears, fars,
                                          ptr(counter, I32, "counter"), ptr(ws), cap, stream_ptr()),
           "march_rays_train_count")
     M = _read_count(counter, while_waiting)
+    if callable(table):
+        table = table(M)
+    if table == RECORDS:
+        t = torch.empty(M, dtype=F32, device=dev)
+        ray_ids = torch.empty(M, dtype=I32, device=dev)
+        check(lib.inr_march_rays_patch_write_records(
+            *args, M, ptr(nears), ptr(fars), ptr(noises, F32, "noises", allow_none=True), ptr(rays),
+            ptr(t, allow_none=M == 0), ptr(ray_ids, allow_none=M == 0), ptr(ws), cap, stream_ptr()),
+            "march_rays_patch_write_records")
+        return t, ray_ids, None, rays
     xyzs = torch.empty(M, 3, dtype=F32, device=dev)       # every row is written: no memset needed
     dirs = None if table else torch.empty(M, 3, dtype=F32, device=dev)
     ray_ids = torch.empty(M, dtype=I32, device=dev) if table else None
@@ -282,11 +298,22 @@ def march_rays_patch(rays_o, rays_d, bound, density_bitfield, C, H, nears, fars,
     return xyzs, (ray_ids if table else dirs), deltas, rays
 
 
-def composite_rays_patch(sigmas, rgbs, deltas, rays, T_thresh=1e-4, extra=None, return_weights=False, skippable=None):
+class MarchRecords:
+    """What the compositing needs beside ``t`` to rebuild (dt, t - t_prev) of the records feed: the ``nears`` [N] and
+    ``noises`` [N] (or None) the rays were marched with, and the step parameters of that march."""
+
+    def __init__(self, nears, noises, dt_gamma, max_steps, C, H):
+        self.nears, self.noises = _f(nears), (_f(noises) if noises is not None else None)
+        self.dt_gamma, self.max_steps, self.C, self.H = float(dt_gamma), int(max_steps), int(C), int(H)
+
+
+def composite_rays_patch(sigmas, rgbs, deltas, rays, T_thresh=1e-4, extra=None, return_weights=False, skippable=None,
+                         records=None):
     """Compositing of the patch-interleaved layout (inference only, no autograd).
     -> weights_sum [N], depth [N], image [N,3] (, extra_out [N,K]) (, weights [M] when return_weights).
     ``skippable`` (int64 [1] on the device, optional) is incremented by the number of samples that lie behind the
-    point where their whole 16-ray group has terminated - what the early-terminating kernel would not evaluate."""
+    point where their whole 16-ray group has terminated - what the early-terminating kernel would not evaluate.
+    ``records`` (a ``MarchRecords``): ``deltas`` is the [M] ``t`` of ``march_rays_patch(table="records")``; same results."""
     lib = _lib.load()
     sigmas, rgbs, deltas = _f(sigmas), _f(rgbs), _f(deltas)
     dev = rays.device
@@ -298,6 +325,19 @@ def composite_rays_patch(sigmas, rgbs, deltas, rays, T_thresh=1e-4, extra=None, 
     extra_out = torch.empty(N, K, dtype=F32, device=dev) if K else None
     wbuf = torch.empty(max(M, 1), dtype=F32, device=dev) if (K or return_weights) else None
     none_ok = M == 0
+    if records is not None:
+        if deltas.dim() != 1 or records.nears.shape[0] != N:
+            raise ValueError("composite_rays_patch(records=): t [M] and the nears of the N marched rays are needed")
+        check(lib.inr_composite_rays_patch_forward_records(
+            ptr(sigmas, F32, "sigmas", allow_none=none_ok), ptr(rgbs, F32, "rgbs", allow_none=none_ok),
+            ptr(deltas, F32, "t", allow_none=none_ok), ptr(rays, I32, "rays"), N, M, float(T_thresh),
+            ptr(records.nears, F32, "nears"), ptr(records.noises, F32, "noises", allow_none=True), records.dt_gamma,
+            records.max_steps, records.C, records.H, ptr(_f(extra) if extra is not None else None, allow_none=True), K,
+            ptr(ws), ptr(depth), ptr(image), ptr(extra_out, allow_none=True), ptr(wbuf, allow_none=True),
+            ptr(skippable, torch.int64, "skippable", allow_none=True), stream_ptr()),
+            "composite_rays_patch_forward_records")
+        out = (ws, depth, image) + ((extra_out,) if K else ())
+        return out + ((wbuf,) if return_weights else ())
     check(lib.inr_composite_rays_patch_forward(
         ptr(sigmas, F32, "sigmas", allow_none=none_ok), ptr(rgbs, F32, "rgbs", allow_none=none_ok),
         ptr(deltas, F32, "deltas", allow_none=none_ok), ptr(rays, I32, "rays"), N, M, float(T_thresh),
