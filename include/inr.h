@@ -449,7 +449,11 @@ int inr_nerf_forward_table(const float* x01, const int32_t* ray_ids, const float
  * INR_RAY_TABLE_FLOATS floats, 16-byte aligned: the 16 values of inr_sh_table_q, then (o, 0) and (d, 0).  Every
  * lane forms x01 = (clamp(o + t d, -bound, bound) + bound) * (1 / (2 bound)) with the marcher's own operations; the
  * product equals the positions writer's division only where 2*bound is a power of two, and any other bound is refused
- * (INR_EINVAL: take the positions feed).  8 instead of 16 bytes are read per sample.                               */
+ * (INR_EINVAL: take the positions feed).  8 instead of 16 bytes are read per sample.
+ * Launches with numerics 0 on a 16-level table whose levels 8..15 are all hashed run behind the pair front end
+ * (k_nerf_fwd_pair: a wave encodes two consecutive tiles in one gather pass, two lanes per sample; same bits).
+ * INR_FIELD_PAIR=0 in the process environment, read at every launch, selects the one-tile kernel for them too - a
+ * switch for A/B measurements and tests, no export and no ABI change.                                               */
 #define INR_RAY_TABLE_FLOATS 24
 int inr_ray_table_q(const float* rays_o /*[N,3]*/, const float* rays_d /*[N,3]*/, int64_t N, float* out, inr_stream_t s);
 int inr_nerf_forward_table_records(const float* t, const int32_t* ray_ids, const float* ray_table_q, int64_t M,

@@ -643,7 +643,12 @@ constexpr int kXcdChunkLog2 = 10;
 #define INR_STEAL_SHIFT 1
 #endif
 constexpr int kStealRoundsShift = INR_STEAL_SHIFT;     // hybrid schedule: the last rounds >> shift rounds are drawn (TileWalk)
-struct TileSched {
+// kUnit: log2 of the tiles one schedule item stands for.  0: an item is a tile.  1 (the pair front end, k_nerf_fwd_pair):
+// an item is a pair of consecutive tiles and the chunks, blocks and draws below halve in items, so that they stay the
+// same runs of tiles - no pair straddles an XCD chunk or a cursor draw.
+template <int kUnit = 0>
+struct TileSchedT {
+  static constexpr int kChunkLog2 = kXcdChunkLog2 - kUnit;
   int64_t lo, hi;      // hi: one past the last tile this wave may take
   int64_t first;       // first tile (contiguous split) or first XCD-local index (interleaved split)
   int64_t stride;      // distance between consecutive tiles / local indices of this wave
@@ -654,7 +659,7 @@ struct TileSched {
   bool interleaved = false, hybrid = false;
   // local index u of XCD y -> tile; one past XCD y's last local index
   __device__ __forceinline__ int64_t tile_of(int y, int64_t u) const {
-    if (u < main_local) return ((((u >> kXcdChunkLog2) << 3) + y) << kXcdChunkLog2) + (u & ((1 << kXcdChunkLog2) - 1));
+    if (u < main_local) return ((((u >> kChunkLog2) << 3) + y) << kChunkLog2) + (u & ((1 << kChunkLog2) - 1));
     return n_main + tail * y / 8 + (u - main_local);
   }
   __device__ __forceinline__ int64_t local_end(int y) const { return main_local + tail * (y + 1) / 8 - tail * y / 8; }
@@ -662,28 +667,31 @@ struct TileSched {
     if (interleaved) {
       const int64_t u = first + i * stride;
       if (u < main_local)
-        return ((((u >> kXcdChunkLog2) << 3) + xcd) << kXcdChunkLog2) + (u & ((1 << kXcdChunkLog2) - 1));
+        return ((((u >> kChunkLog2) << 3) + xcd) << kChunkLog2) + (u & ((1 << kChunkLog2) - 1));
       return tail_base + (u - main_local);
     }
     return first + i * stride;
   }
 };
-__device__ __forceinline__ TileSched make_sched(int64_t n_tiles, int waves_per_block, bool steal = false) {
+using TileSched = TileSchedT<>;
+template <int kUnit = 0>
+__device__ __forceinline__ TileSchedT<kUnit> make_sched(int64_t n_tiles, int waves_per_block, bool steal = false) {
+  constexpr int kChunkLog2 = TileSchedT<kUnit>::kChunkLog2;
   const int nb = gridDim.x, b = blockIdx.x;
   const int w = threadIdx.x >> 6;
-  TileSched s;
+  TileSchedT<kUnit> s;
   if (nb % 8 == 0) {
     const int xcd = b & 7, local = b >> 3, per = nb >> 3;
-    const int64_t rounds = n_tiles >> (kXcdChunkLog2 + 3);
+    const int64_t rounds = n_tiles >> (kChunkLog2 + 3);
     if (rounds >= 4) {
-      const int64_t n_main = rounds << (kXcdChunkLog2 + 3), tail = n_tiles - n_main;
+      const int64_t n_main = rounds << (kChunkLog2 + 3), tail = n_tiles - n_main;
       s.interleaved = true;
       s.xcd = (uint32_t)xcd;
-      s.main_local = rounds << kXcdChunkLog2;
+      s.main_local = rounds << kChunkLog2;
       s.n_main = n_main;
       s.tail = tail;
       s.hybrid = steal;
-      s.static_local = steal ? (rounds - max((int64_t)1, rounds >> kStealRoundsShift)) << kXcdChunkLog2 : s.main_local;
+      s.static_local = steal ? (rounds - max((int64_t)1, rounds >> kStealRoundsShift)) << kChunkLog2 : s.main_local;
       s.tail_base = n_main + tail * xcd / 8;
       s.lo = 0;
       s.hi = n_main + tail * (xcd + 1) / 8;
@@ -757,15 +765,17 @@ struct GroupDraw {
 // 5.12 ms, a quarter / half / all of the rounds drawn 4.88 / 4.85 / 4.91 ms; with one XCD made ~64 % slower
 // (s_sleep per tile) 8.51 / 6.35 / 5.17 / 5.23 ms - half it is (kStealRoundsShift = 1).
 constexpr int kStealPools = 4, kStealOwners = 8 * kStealPools, kStealDraw = 4, kStealBlockLog2 = 6;
-struct TileWalk {
-  TileSched s;
+template <int kUnit = 0>
+struct TileWalkT {
+  static constexpr int kBlockLog2 = kStealBlockLog2 - kUnit, kDraw = kStealDraw >> kUnit;     // in items (TileSchedT)
+  TileSchedT<kUnit> s;
   unsigned long long* cur;
   int lane, own, owner, sub;
   int64_t it, k_base;
   unsigned long long raw_next;           // the draw in flight (lane 0), not looked at until it is needed
   bool dyn;
-  __device__ __forceinline__ void init(const TileSched& sched, unsigned long long* cursors) {
-    s = sched; cur = cursors; lane = threadIdx.x & 63; it = 0; dyn = false; sub = kStealDraw; k_base = 0; raw_next = 0;
+  __device__ __forceinline__ void init(const TileSchedT<kUnit>& sched, unsigned long long* cursors) {
+    s = sched; cur = cursors; lane = threadIdx.x & 63; it = 0; dyn = false; sub = kDraw; k_base = 0; raw_next = 0;
     own = owner = (int)(((blockIdx.x >> 3) % kStealPools) * 8 + (blockIdx.x & 7));
     if (!cursors) s.hybrid = false;
     if (!s.hybrid) s.static_local = s.main_local;
@@ -773,17 +783,17 @@ struct TileWalk {
   // owner o = pool * 8 + xcd: number of cursor positions that map to local indices below the XCD's end (a multiple of
   // the block), and the local index of position k
   __device__ __forceinline__ int64_t pool_len(int o) const {
-    const int64_t nb = (s.local_end(o & 7) - s.static_local + (1 << kStealBlockLog2) - 1) >> kStealBlockLog2;
+    const int64_t nb = (s.local_end(o & 7) - s.static_local + (1 << kBlockLog2) - 1) >> kBlockLog2;
     const int p = o >> 3;
-    return nb > p ? ((nb - p + kStealPools - 1) / kStealPools) << kStealBlockLog2 : 0;
+    return nb > p ? ((nb - p + kStealPools - 1) / kStealPools) << kBlockLog2 : 0;
   }
   __device__ __forceinline__ int64_t local_of(int o, int64_t k) const {
-    return s.static_local + ((((k >> kStealBlockLog2) * kStealPools) + (o >> 3)) << kStealBlockLog2) +
-           (k & ((1 << kStealBlockLog2) - 1));
+    return s.static_local + ((((k >> kBlockLog2) * kStealPools) + (o >> 3)) << kBlockLog2) +
+           (k & ((1 << kBlockLog2) - 1));
   }
   __device__ __forceinline__ unsigned long long issue(int o) const {
     unsigned long long v = 0;
-    if (lane == 0) v = atomicAdd(cur + o, (unsigned long long)kStealDraw);
+    if (lane == 0) v = atomicAdd(cur + o, (unsigned long long)kDraw);
     return v;
   }
   __device__ __forceinline__ static int64_t uniform(unsigned long long v) {
@@ -814,7 +824,7 @@ struct TileWalk {
       raw_next = issue(owner);
     }
     for (;;) {
-      if (sub < kStealDraw) {
+      if (sub < kDraw) {
         const int64_t u = local_of(owner, k_base + sub);
         ++sub;
         if (u < s.local_end(owner & 7)) return s.tile_of(owner & 7, u);
@@ -833,6 +843,7 @@ struct TileWalk {
     }
   }
 };
+using TileWalk = TileWalkT<>;
 constexpr int kFieldMinWaves = 2;      // __launch_bounds__ second argument: <= 128 VGPRs
 
 // kTable: fused-frame fast path - x is already normalised to [0,1] by the march writer and the direction
@@ -1027,6 +1038,251 @@ __global__ void __launch_bounds__(kFieldThreads, kFieldMinWaves) k_nerf_fwd(cons
     }
   }
   INR_PROBE_EPILOGUE();
+}
+
+// ---- pair front end of the frame kernel: two tiles per gather pass, two lanes per sample ----------------------------
+// Consecutive tiles of the patch-interleaved sample stream are consecutive steps of the same 16 rays, one dt apart, and
+// touch many of the same 128-byte lines of the table - but k_nerf_fwd asks for them in separate instructions, and a line
+// touched by two instructions is looked up twice (see the note on the lane-paired gather above).  Here a wave encodes
+// the 32 samples of tiles (2p, 2p+1) in ONE instruction stream and then runs the MLP of k_nerf_fwd once per tile.
+// tools/pair_line_model.py counts the distinct lines per instruction both ways on the bench geometry: 0.73-0.78.
+// Measured (profiles/r09_pair_gather_bench.md): L1 accesses fall by 5 % only, but the L1's read requests to the L2 by
+// 21 % and the waves' wait cycles by a third - the second tile finds its lines while they are still there.
+// Encoder lane map: lane = 32 h + 16 s + j - tile h of the pair, sample j, s in {0, 1}.
+//   coarse: lane s owns levels {0,1,4,5} (s = 0) or {2,3,6,7} (s = 1), eight corners each, blended in corner order;
+//   fine:   lane s fetches x side s of ALL eight levels 8..15, four yz corners each, blends its side in yz order, and
+//           the sides meet by v_permlane16_swap + add: lane s = 0 ends with levels {8,9,12,13}, s = 1 with {10,11,14,15}.
+// 64 gathers per lane and pair - 32 per tile as before - but every fine instruction now covers 32 samples x both x sides
+// of one level and every coarse instruction 32 samples x two levels; a lane locates 12 cells per pair instead of 2 x 6.
+// Every operation of a (sample, level) and its order are k_nerf_fwd's: the results are the same bits.
+// Hand-over: rows 0/1 (lanes 0..31) hold what lanes q = 0, 1 of tile A need; one v_permlane32_swap per register on the
+// eight features of levels {4,5,12,13} / {6,7,14,15} (vdst = the register of levels {0,1,8,9} / {2,3,10,11}) moves tile
+// A's to rows 2/3 and brings tile B's rows to the front: afterwards vdst is tile A's and src tile B's encoding in the
+// MLP's layout (lane q owns levels {2q, 2q+1, 8+2q, 9+2q}).
+// The fine levels are hashed for every launch that gets here (the host checks), so their constants are the primes and
+// three wave-uniform words per level straight from the kernel arguments - no LDS record reads for them.
+// Staging: 32 coarse + 16 fine gathers go out, the coarse levels are blended under those fine loads, then the other 16
+// fine gathers, then the fine blend - at most 48 rows (96 registers) are held at once.  All 64 rows held until one
+// blend at the end needs 242 VGPRs: two such waves fill a SIMD's 512 registers, the next view's marchers find no room
+// on any CU and the frame loop LOSES 1 % although the kernel itself is 14 % faster; this form needs 196 and leaves the
+// marchers the wave per SIMD they had.  Waits (INR_PAIR_WAIT_*, as in issue_gathers_impl) swept again for this form:
+// 16 / 8 here; 8 / 4, 32 / 16, 16 / 4 and none are 0.4-1.2 % slower (profiles/r09_pair_gather_bench.md).
+#ifndef INR_PAIR_WAIT_COARSE
+#define INR_PAIR_WAIT_COARSE 16
+#endif
+#ifndef INR_PAIR_WAIT_FINE
+#define INR_PAIR_WAIT_FINE 8
+#endif
+constexpr int kPairWaitAfterCoarse = INR_PAIR_WAIT_COARSE;      // loads still in flight when the first fine level goes out
+constexpr int kPairWaitBetweenFine = INR_PAIR_WAIT_FINE;        // ... and when each later fine level goes out
+struct GatheredPair {
+  u32x2 c[4][8];      // coarse: raw rows [slot][corner]; slot c is level 4 (c >> 1) + 2 s + (c & 1)
+  u32x2 f[8][4];      // fine: this lane's x side of level 8 + i, [i][yz corner]
+  float cfx[4], cfy[4], cfz[4];
+  float fwx[8], ffy[8], ffz[8];
+};
+
+// my_recs: the records of levels 2 s, 2 s + 1 (q = s); those of levels 4 + 2 s, 5 + 2 s (q = 2 + s) lie 8 records on
+__device__ __forceinline__ void issue_coarse_pair(const LevelRec* __restrict__ my_recs, __amdgpu_buffer_rsrc_t rsrc, float x0,
+                                                  float x1, float x2, GatheredPair& g) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const LevelRec* rec = my_recs + (c >> 1) * 8 + (c & 1);
+    const uint4 ra = rec->a;
+    const float s = __uint_as_float(ra.x);
+    const uint32_t base = ra.y, pa = ra.z, pb = ra.w;
+    const uint4 rb = rec->b;
+    const uint32_t mask = rb.x;
+    const float px = x0 * s + 0.5f, py = x1 * s + 0.5f, pz = x2 * s + 0.5f;   // mul, add: not fused
+    g.cfx[c] = __builtin_amdgcn_fractf(px); g.cfy[c] = __builtin_amdgcn_fractf(py); g.cfz[c] = __builtin_amdgcn_fractf(pz);
+    const uint32_t cx = (uint32_t)px, cy = (uint32_t)py, cz = (uint32_t)pz;
+    const uint32_t hy0 = cy * pa, hy1 = hy0 + pa;
+    const uint32_t hz0 = cz * pb, hz1 = hz0 + pb;
+    const IndexTerms t = index_terms(hy0, hy1, hz0, hz1, rb.z, rb.w);
+    uint32_t off[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) off[k] = base + t.row(cx + (k & 1), k >> 1, mask) * 8u;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) g.c[c][k] = gather_at(rsrc, off[k]);
+    keep_offsets(off[0], off[1], off[2], off[3]);
+    keep_offsets(off[4], off[5], off[6], off[7]);
+  }
+}
+
+// fine levels 8 + kFirst .. 8 + kFirst + 3
+template <int kFirst>
+__device__ __forceinline__ void issue_fine_pair(const GridDesc& G, __amdgpu_buffer_rsrc_t rsrc, uint32_t side, float x0, float x1,
+                                                float x2, GatheredPair& g) {
+#pragma unroll
+  for (int i = kFirst; i < kFirst + 4; ++i) {
+    const float s = G.scales[8 + i];
+    const uint32_t base = G.offsets[8 + i] * 8u, mask = G.mask[8 + i];
+    const uint32_t pa = 2654435761u, pb = 805459861u;
+    const float px = x0 * s + 0.5f, py = x1 * s + 0.5f, pz = x2 * s + 0.5f;
+    const float fx = __builtin_amdgcn_fractf(px);
+    g.fwx[i] = side ? fx : 1.0f - fx;
+    g.ffy[i] = __builtin_amdgcn_fractf(py); g.ffz[i] = __builtin_amdgcn_fractf(pz);
+    const uint32_t c = (uint32_t)px + side, cy = (uint32_t)py, cz = (uint32_t)pz;
+    const uint32_t hy0 = cy * pa, hy1 = hy0 + pa;
+    const uint32_t hz0 = cz * pb, hz1 = hz0 + pb;
+    if (i == 0) wait_vmcnt<kPairWaitAfterCoarse>();
+    else wait_vmcnt<kPairWaitBetweenFine>();
+    uint32_t off[4];           // byte offsets of the rows (y0z0, y1z0, y0z1, y1z1)
+    off[0] = base + ((c ^ (hy0 ^ hz0)) & mask) * 8u;
+    off[1] = base + ((c ^ (hy1 ^ hz0)) & mask) * 8u;
+    off[2] = base + ((c ^ (hy0 ^ hz1)) & mask) * 8u;
+    off[3] = base + ((c ^ (hy1 ^ hz1)) & mask) * 8u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) g.f[i][k] = gather_at(rsrc, off[k]);
+    keep_offsets(off[0], off[1], off[2], off[3]);
+  }
+}
+
+// p[0], p[1]: this lane's features of levels {2s, 2s+1}, {8+2s, 9+2s} - enc[0], enc[1] of MLP lane q = s;
+// r[0], r[1]: of levels {4+2s, 5+2s}, {12+2s, 13+2s} - those of MLP lane q = 2 + s.  Operations: blend()'s.
+__device__ __forceinline__ void blend_coarse_pair(const GatheredPair& g, f32x4 (&p)[2], f32x4 (&r)[2]) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const f32x2 wx = {1.0f - g.cfx[c], g.cfx[c]};
+    const float wy0 = 1.0f - g.cfy[c], wz0 = 1.0f - g.cfz[c];
+    const f32x2 a = wx * wy0, b = wx * g.cfy[c];
+    const f32x2 w[4] = {a * wz0, b * wz0, a * g.cfz[c], b * g.cfz[c]};
+    f32x2 acc = {0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const f32x2 wk = (k & 1) ? w[k >> 1].yy : w[k >> 1].xx;
+      acc = __builtin_elementwise_fma(wk, row2(g.c[c][k]), acc);
+    }
+    f32x4& out = (c >> 1) ? r[0] : p[0];
+    out[2 * (c & 1)] = acc.x;
+    out[2 * (c & 1) + 1] = acc.y;
+  }
+}
+__device__ __forceinline__ void blend_fine_pair(const GatheredPair& g, f32x4 (&p)[2], f32x4 (&r)[2]) {
+  f32x2 part[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const f32x2 wy = {1.0f - g.ffy[i], g.ffy[i]};
+    const f32x2 xy = wy * g.fwx[i];
+    const f32x2 w0 = xy * (1.0f - g.ffz[i]), w1 = xy * g.ffz[i];
+    f32x2 acc = {0.f, 0.f};
+    acc = __builtin_elementwise_fma(w0.xx, row2(g.f[i][0]), acc);
+    acc = __builtin_elementwise_fma(w0.yy, row2(g.f[i][1]), acc);
+    acc = __builtin_elementwise_fma(w1.xx, row2(g.f[i][2]), acc);
+    acc = __builtin_elementwise_fma(w1.yy, row2(g.f[i][3]), acc);
+    part[i] = acc;
+  }
+  // as in blend(): vdst = the partial of a level the s = 0 lanes end up with, src = of one the s = 1 lanes end up with
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const int i0 = (k >> 1) * 4 + (k & 1);      // levels 8, 9, 12, 13 (s = 0) | + 2 (s = 1)
+#pragma unroll
+    for (int ft = 0; ft < 2; ++ft) {
+      const auto v = __builtin_amdgcn_permlane16_swap(__float_as_uint(part[i0][ft]), __float_as_uint(part[i0 + 2][ft]), false, false);
+      const unsigned v0 = v[0], v1 = v[1];
+      f32x4& out = (k >> 1) ? r[1] : p[1];
+      out[2 * (k & 1) + ft] = __uint_as_float(v0) + __uint_as_float(v1);      // = x side 0 + x side 1 in both lanes
+    }
+  }
+}
+
+// MLP, epilogue and stores of one tile: k_nerf_fwd<true, true>'s, operation by operation (no geo output, nothing saved)
+__device__ __forceinline__ void pair_tile_mlp(const float4* __restrict__ wl, int lane, bool valid, int64_t m, const f32x4 (&enc)[2],
+                                              f32x4 sh_in, float density_scale, float* __restrict__ sigma,
+                                              float* __restrict__ rgb) {
+  const int q = lane >> 4;
+  f32x4 h1[4];
+  mlp_layer<4, 2>(wl + kSig0 / 4, lane, enc, h1);
+#pragma unroll
+  for (int t = 0; t < 4; ++t) h1[t] = relu4(h1[t]);
+  f32x4 h2[1];
+  mlp_layer<1, 4>(wl + kSig1 / 4, lane, h1, h2);
+  if (valid && q == 0) sigma[m] = __expf(h2[0][0]) * density_scale;
+  f32x4 cin[2] = {sh_in, h2[0]};
+  f32x4 c1[4], c2[4], o[1];
+  mlp_layer<4, 2>(wl + kCol0 / 4, lane, cin, c1);
+#pragma unroll
+  for (int t = 0; t < 4; ++t) c1[t] = relu4(c1[t]);
+  mlp_layer<4, 4>(wl + kCol1 / 4, lane, c1, c2);
+#pragma unroll
+  for (int t = 0; t < 4; ++t) c2[t] = relu4(c2[t]);
+  mlp_layer<1, 4>(wl + kCol2 / 4, lane, c2, o);
+  const float ch = sigmoid_rgb(rgb_channel_of_lane(o[0]));
+  if (valid && q < 3) rgb[m * 3 + q] = ch;
+}
+
+// The records feed of k_nerf_fwd<true, true, 0, false, false, false, true> behind the pair front end; same arguments
+// where it has them.  The host takes it only for a 16-level fp32 table whose levels 8..15 are all hashed.
+__global__ void __launch_bounds__(kFieldThreads, kFieldMinWaves) k_nerf_fwd_pair(
+    const float* __restrict__ x, int64_t M, float bound, const float2* __restrict__ emb, uint32_t emb_bytes, GridDesc G,
+    const float4* __restrict__ packed, float density_scale, float* __restrict__ sigma, float* __restrict__ rgb,
+    const int32_t* __restrict__ ray_ids, const float4* __restrict__ shq, unsigned long long* __restrict__ steal) {
+  extern __shared__ __attribute__((aligned(16))) float4 wl[];
+  __builtin_amdgcn_s_setprio(3);
+  constexpr int kStage = kNerfFloats / 4;
+  for (int i = threadIdx.x; i < kStage; i += kFieldThreads) wl[i] = packed[i];
+  LevelRec* recs = reinterpret_cast<LevelRec*>(wl + kStage);
+  stage_level_recs(G, recs);
+  __syncthreads();
+
+  constexpr int kWaves = kFieldThreads / 64;
+  const int lane = threadIdx.x & 63, q = lane >> 4, j = lane & 15, h = lane >> 5;
+  const uint32_t side = (uint32_t)(q & 1);
+  const int64_t n = M;
+  const int64_t n_tiles = (n + 15) >> 4, n_pairs = (n_tiles + 1) >> 1;     // an odd last tile: a pair with an invalid half
+  const float rb_rcp = 1.0f / (2.0f * bound);                               // exact: 2 * bound is a power of two
+  TileWalkT<1> walk;
+  walk.init(make_sched<1>(n_pairs, kWaves, steal != nullptr), steal);
+  const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void*)emb, 0, (int)emb_bytes, 0x00020000);
+
+  for (int64_t pair = walk.next(); pair >= 0; pair = walk.next()) {
+    // encoder layout: t, ray id, origin and direction of sample j of tile h, once per pair
+    const int64_t mg = pair * 32 + h * 16 + j;
+    const int64_t mm = mg < n ? mg : n - 1;
+    const float t = x[mm];
+    const int32_t rid = ray_ids[mm];
+    const float4* row = shq + (int64_t)rid * kRayRowVec;
+    const float4 o4 = row[4], d4 = row[5];
+    // MLP layout: lanes (q, j) of tile A / B need sample j's SH row q - the ray ids of the lower / upper half-wave
+    const auto rr = __builtin_amdgcn_permlane32_swap((unsigned)rid, (unsigned)rid, false, false);
+    const unsigned rid_a = rr[0], rid_b = rr[1];
+    const float4 sa = shq[(int64_t)(int32_t)rid_a * kRayRowVec + q], sb = shq[(int64_t)(int32_t)rid_b * kRayRowVec + q];
+    const float x0 = sample_x01_pow2(sample_pos(o4.x, t, d4.x, bound), bound, rb_rcp);
+    const float x1 = sample_x01_pow2(sample_pos(o4.y, t, d4.y, bound), bound, rb_rcp);
+    const float x2 = sample_x01_pow2(sample_pos(o4.z, t, d4.z, bound), bound, rb_rcp);
+
+    f32x4 enc_a[2], enc_b[2];
+    {
+      GatheredPair g;
+      uint32_t rec_off = side * 4u * (uint32_t)sizeof(LevelRec);
+      asm volatile("" : "+v"(rec_off));    // opaque per pair: keeps the records in LDS, not hoisted into VGPRs
+      // 32 coarse + 16 fine gathers out, the coarse blend under the fine loads, then the other 16: at most 48 rows
+      // (96 registers) are held at once, which leaves the marchers of the next view their registers on the CU
+      issue_coarse_pair(reinterpret_cast<const LevelRec*>(reinterpret_cast<const char*>(recs) + rec_off), rsrc, x0, x1, x2, g);
+      issue_fine_pair<0>(G, rsrc, side, x0, x1, x2, g);
+      __builtin_amdgcn_sched_barrier(0);
+      blend_coarse_pair(g, enc_a, enc_b);
+      __builtin_amdgcn_sched_barrier(0);
+      issue_fine_pair<4>(G, rsrc, side, x0, x1, x2, g);
+      __builtin_amdgcn_sched_barrier(0);
+      blend_fine_pair(g, enc_a, enc_b);
+    }
+#pragma unroll
+    for (int e = 0; e < 2; ++e) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        const auto v = __builtin_amdgcn_permlane32_swap(__float_as_uint(enc_a[e][c]), __float_as_uint(enc_b[e][c]), false, false);
+        const unsigned v0 = v[0], v1 = v[1];
+        enc_a[e][c] = __uint_as_float(v0);
+        enc_b[e][c] = __uint_as_float(v1);
+      }
+    }
+
+    const int64_t ma = pair * 32 + j, mb = ma + 16;
+    pair_tile_mlp(wl, lane, ma < n, ma, enc_a, f32x4{sa.x, sa.y, sa.z, sa.w}, density_scale, sigma, rgb);
+    if (pair * 2 + 1 < n_tiles)
+      pair_tile_mlp(wl, lane, mb < n, mb, enc_b, f32x4{sb.x, sb.y, sb.z, sb.w}, density_scale, sigma, rgb);
+  }
 }
 
 // ---- sliced frame path: the finest levels level by level (round 5) ---------------------------------------------------
@@ -2824,6 +3080,20 @@ static void pack_section_as(int32_t numerics, float* dst, const float* W, int n_
 // The fused table launch behind inr_nerf_forward_table (kRec false: x = x01 [M,3], table = the SH rows) and
 // inr_nerf_forward_table_records (kRec true: x = t [M], table = the ray rows): one LDS request, priority, tile schedule and
 // cursor set for both - only where a tile's coordinates come from differs.
+// k_nerf_fwd_pair serves the frame path's default variant only: records feed, 16-level fp32 table with every fine level
+// (8..15) hashed, bf16x3 MLP.  INR_FIELD_PAIR=0 in the environment - read at every launch, so that one process can run
+// both - selects k_nerf_fwd for those launches too (same bits; for A/B measurements and the tests).
+static bool pair_front_end_qualifies(const inr_grid_desc* desc, int32_t numerics) {
+#if INR_MLP_FP32
+  return false;
+#endif
+  if (numerics != 0 || desc->num_levels != 16) return false;
+  for (int l = 8; l < 16; ++l)
+    if (!desc->hashed[l]) return false;
+  const char* off = getenv("INR_FIELD_PAIR");
+  return !(off && off[0] == '0' && off[1] == 0);
+}
+
 template <bool kRec>
 static int forward_table_launch(const char* what, const float* x, const int32_t* ray_ids, const float* table, int64_t M,
                                 float bound, const void* embeddings, const inr_grid_desc* desc, const float* packed,
@@ -2836,6 +3106,12 @@ static int forward_table_launch(const char* what, const float* x, const int32_t*
   const hipStream_t st = as_stream(s);
   HybridSchedule hybrid;         // frames (four rounds of eight 1024-tile chunks and more)
   if (!hybrid.begin(st, n_tiles)) return INR_ELAUNCH;
+  if (kRec && pair_front_end_qualifies(desc, numerics)) {
+    launch_field(k_nerf_fwd_pair, lds, (n_tiles + 1) / 2, st, x, M, bound, t.emb, t.bytes, t.G, f4(packed), density_scale,
+                 sigma, rgb, ray_ids, f4(table), hybrid.cursors());
+    hybrid.finish(st);
+    return check_launch(what + 4);
+  }
   with_flag(numerics & INR_NUMERICS_TABLE_F16, [&](auto half) {
     with_mlp_f16(numerics & INR_NUMERICS_MLP_F16, [&](auto fast) {
       launch_field(k_nerf_fwd<true, true, 0, decltype(half)::value, decltype(fast)::value, false, kRec>, lds, n_tiles, st,
