@@ -573,6 +573,86 @@ __device__ __forceinline__ void mlp_layer(const float4* __restrict__ wsec, int l
 #endif
 }
 
+// ---- two tiles through one layer (k_nerf_fwd_pair) -------------------------------------------------------------------
+// layer_bf for tiles A and B at once: every (mt, step, hi|lo) weight fragment is read from LDS ONCE and feeds A's and
+// B's MFMA back to back - two independent accumulator chains per output tile.  Per tile, the operands and their order
+// are layer_bf's (per step hi.hi, lo.hi, hi.lo on that tile's own accumulator; a0 + (a1 + a2) for one output tile).
+template <int N_MT, int N_S>
+__device__ __forceinline__ void layer_bf2(const uint4* __restrict__ w, int lane, const SplitB* in_a, const SplitB* in_b,
+                                          f32x4* out_a, f32x4* out_b) {
+  if constexpr (N_MT == 1) {
+    f32x4 a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, b0 = a0, b1 = a0, b2 = a0;
+#pragma unroll
+    for (int st = 0; st < N_S; ++st) {
+      __builtin_amdgcn_sched_barrier(0);
+      const uint4 wh = w[(st * 2 + 0) * 64 + lane], wlo = w[(st * 2 + 1) * 64 + lane];
+      a0 = mfma_bf(wh, in_a[st].hi, a0);
+      b0 = mfma_bf(wh, in_b[st].hi, b0);
+      a1 = mfma_bf(wlo, in_a[st].hi, a1);
+      b1 = mfma_bf(wlo, in_b[st].hi, b1);
+      a2 = mfma_bf(wh, in_a[st].lo, a2);
+      b2 = mfma_bf(wh, in_b[st].lo, b2);
+    }
+    out_a[0] = a0 + (a1 + a2);
+    out_b[0] = b0 + (b1 + b2);
+  } else {
+    f32x4 acc_a[N_MT], acc_b[N_MT];
+#pragma unroll
+    for (int mt = 0; mt < N_MT; ++mt) acc_a[mt] = acc_b[mt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int st = 0; st < N_S; ++st) {
+      __builtin_amdgcn_sched_barrier(0);   // keep weight reads next to their MFMAs (register pressure)
+      uint4 wh[N_MT], wlo[N_MT];
+#pragma unroll
+      for (int mt = 0; mt < N_MT; ++mt) {
+        wh[mt] = w[((mt * N_S + st) * 2 + 0) * 64 + lane];
+        wlo[mt] = w[((mt * N_S + st) * 2 + 1) * 64 + lane];
+      }
+#pragma unroll
+      for (int mt = 0; mt < N_MT; ++mt) {
+        acc_a[mt] = mfma_bf(wh[mt], in_a[st].hi, acc_a[mt]);
+        acc_b[mt] = mfma_bf(wh[mt], in_b[st].hi, acc_b[mt]);
+      }
+#pragma unroll
+      for (int mt = 0; mt < N_MT; ++mt) {
+        acc_a[mt] = mfma_bf(wlo[mt], in_a[st].hi, acc_a[mt]);
+        acc_b[mt] = mfma_bf(wlo[mt], in_b[st].hi, acc_b[mt]);
+      }
+#pragma unroll
+      for (int mt = 0; mt < N_MT; ++mt) {
+        acc_a[mt] = mfma_bf(wh[mt], in_a[st].lo, acc_a[mt]);
+        acc_b[mt] = mfma_bf(wh[mt], in_b[st].lo, acc_b[mt]);
+      }
+    }
+#pragma unroll
+    for (int mt = 0; mt < N_MT; ++mt) {
+      out_a[mt] = acc_a[mt];
+      out_b[mt] = acc_b[mt];
+    }
+  }
+}
+
+// mlp_layer (default numerics) for two tiles.  (The exact-fp32 A/B library keeps one tile per layer call.)
+// The split stays split8's two v_sub_f32 per pair of values.  A packed form - both remainders from one 2-vector
+// subtraction, v_pk_add_f32 with neg: 64 VALU fewer per pair, the same bits - was measured beside this one and is NOT
+// faster (profiles/r10_pair_mlp_bench.md): a packed f32 instruction next to MFMAs costs more than the two it replaces.
+template <int N_MT, int N_G>
+__device__ __forceinline__ void mlp_layer2(const float4* __restrict__ wsec, int lane, const f32x4* in_a, const f32x4* in_b,
+                                           f32x4* out_a, f32x4* out_b) {
+#if INR_MLP_FP32
+  layer<N_MT, N_G>(wsec, lane, in_a, out_a);
+  layer<N_MT, N_G>(wsec, lane, in_b, out_b);
+#else
+  SplitB a[N_G / 2], b[N_G / 2];
+#pragma unroll
+  for (int st = 0; st < N_G / 2; ++st) {
+    a[st] = split8(in_a[2 * st], in_a[2 * st + 1]);
+    b[st] = split8(in_b[2 * st], in_b[2 * st + 1]);
+  }
+  layer_bf2<N_MT, N_G / 2>(reinterpret_cast<const uint4*>(wsec), lane, a, b, out_a, out_b);
+#endif
+}
+
 // Colour epilogue.  The last layer leaves the three pre-activations of sample j in registers 0..2 of its lane q = 0
 // (rows 0..2 of D, both MFMA shapes).  Evaluating three sigmoids there costs three exp + three IEEE divisions - 49 VALU
 // instructions, 6 of them transcendental - on a quarter of the lanes, and the exec mask saves no issue slot.  Two
@@ -1044,7 +1124,11 @@ __global__ void __launch_bounds__(kFieldThreads, kFieldMinWaves) k_nerf_fwd(cons
 // Consecutive tiles of the patch-interleaved sample stream are consecutive steps of the same 16 rays, one dt apart, and
 // touch many of the same 128-byte lines of the table - but k_nerf_fwd asks for them in separate instructions, and a line
 // touched by two instructions is looked up twice (see the note on the lane-paired gather above).  Here a wave encodes
-// the 32 samples of tiles (2p, 2p+1) in ONE instruction stream and then runs the MLP of k_nerf_fwd once per tile.
+// the 32 samples of tiles (2p, 2p+1) in ONE instruction stream and then runs the MLP of k_nerf_fwd on both tiles in ONE
+// pass over the weights (pair_mlp / mlp_layer2: every weight fragment is read from LDS once per pair and feeds tile A's
+// and tile B's MFMA back to back; per tile the operations and their order are k_nerf_fwd's).  Per pair in the hot loop:
+// 52 LDS reads instead of 92, 60 s_waitcnt instead of 95, the same 120 MFMAs; frame loop +1.5 %
+// (profiles/r10_pair_mlp_bench.md, r10_pair_mlp_isa.md).
 // tools/pair_line_model.py counts the distinct lines per instruction both ways on the bench geometry: 0.73-0.78.
 // Measured (profiles/r09_pair_gather_bench.md): L1 accesses fall by 5 % only, but the L1's read requests to the L2 by
 // 21 % and the waves' wait cycles by a third - the second tile finds its lines while they are still there.
@@ -1186,29 +1270,44 @@ __device__ __forceinline__ void blend_fine_pair(const GatheredPair& g, f32x4 (&p
   }
 }
 
-// MLP, epilogue and stores of one tile: k_nerf_fwd<true, true>'s, operation by operation (no geo output, nothing saved)
-__device__ __forceinline__ void pair_tile_mlp(const float4* __restrict__ wl, int lane, bool valid, int64_t m, const f32x4 (&enc)[2],
-                                              f32x4 sh_in, float density_scale, float* __restrict__ sigma,
-                                              float* __restrict__ rgb) {
+// MLP, epilogue and stores of both tiles of a pair in one pass over the weights (mlp_layer2): per tile it is
+// k_nerf_fwd<true, true>'s, operation by operation (no geo output, nothing saved) - the two tiles share the weight
+// fragments read from LDS and nothing else; no value of one tile enters an operation of the other.  An odd last tile's
+// invalid half B runs on the clamped samples (row n - 1) like the invalid rows of a ragged tile: its stores are masked.
+__device__ __forceinline__ void pair_mlp(const float4* __restrict__ wl, int lane, bool valid_a, bool valid_b, int64_t ma,
+                                         int64_t mb, const f32x4 (&enc_a)[2], const f32x4 (&enc_b)[2], f32x4 sh_a, f32x4 sh_b,
+                                         float density_scale, float* __restrict__ sigma, float* __restrict__ rgb) {
   const int q = lane >> 4;
-  f32x4 h1[4];
-  mlp_layer<4, 2>(wl + kSig0 / 4, lane, enc, h1);
+  f32x4 h1a[4], h1b[4];
+  mlp_layer2<4, 2>(wl + kSig0 / 4, lane, enc_a, enc_b, h1a, h1b);
 #pragma unroll
-  for (int t = 0; t < 4; ++t) h1[t] = relu4(h1[t]);
-  f32x4 h2[1];
-  mlp_layer<1, 4>(wl + kSig1 / 4, lane, h1, h2);
-  if (valid && q == 0) sigma[m] = __expf(h2[0][0]) * density_scale;
-  f32x4 cin[2] = {sh_in, h2[0]};
-  f32x4 c1[4], c2[4], o[1];
-  mlp_layer<4, 2>(wl + kCol0 / 4, lane, cin, c1);
+  for (int t = 0; t < 4; ++t) {
+    h1a[t] = relu4(h1a[t]);
+    h1b[t] = relu4(h1b[t]);
+  }
+  f32x4 h2a[1], h2b[1];
+  mlp_layer2<1, 4>(wl + kSig1 / 4, lane, h1a, h1b, h2a, h2b);
+  if (valid_a && q == 0) sigma[ma] = __expf(h2a[0][0]) * density_scale;
+  if (valid_b && q == 0) sigma[mb] = __expf(h2b[0][0]) * density_scale;
+  const f32x4 cin_a[2] = {sh_a, h2a[0]}, cin_b[2] = {sh_b, h2b[0]};
+  f32x4 c1a[4], c1b[4], c2a[4], c2b[4], oa[1], ob[1];
+  mlp_layer2<4, 2>(wl + kCol0 / 4, lane, cin_a, cin_b, c1a, c1b);
 #pragma unroll
-  for (int t = 0; t < 4; ++t) c1[t] = relu4(c1[t]);
-  mlp_layer<4, 4>(wl + kCol1 / 4, lane, c1, c2);
+  for (int t = 0; t < 4; ++t) {
+    c1a[t] = relu4(c1a[t]);
+    c1b[t] = relu4(c1b[t]);
+  }
+  mlp_layer2<4, 4>(wl + kCol1 / 4, lane, c1a, c1b, c2a, c2b);
 #pragma unroll
-  for (int t = 0; t < 4; ++t) c2[t] = relu4(c2[t]);
-  mlp_layer<1, 4>(wl + kCol2 / 4, lane, c2, o);
-  const float ch = sigmoid_rgb(rgb_channel_of_lane(o[0]));
-  if (valid && q < 3) rgb[m * 3 + q] = ch;
+  for (int t = 0; t < 4; ++t) {
+    c2a[t] = relu4(c2a[t]);
+    c2b[t] = relu4(c2b[t]);
+  }
+  mlp_layer2<1, 4>(wl + kCol2 / 4, lane, c2a, c2b, oa, ob);
+  const float ch_a = sigmoid_rgb(rgb_channel_of_lane(oa[0]));
+  const float ch_b = sigmoid_rgb(rgb_channel_of_lane(ob[0]));
+  if (valid_a && q < 3) rgb[ma * 3 + q] = ch_a;
+  if (valid_b && q < 3) rgb[mb * 3 + q] = ch_b;
 }
 
 // The records feed of k_nerf_fwd<true, true, 0, false, false, false, true> behind the pair front end; same arguments
@@ -1279,9 +1378,8 @@ __global__ void __launch_bounds__(kFieldThreads, kFieldMinWaves) k_nerf_fwd_pair
     }
 
     const int64_t ma = pair * 32 + j, mb = ma + 16;
-    pair_tile_mlp(wl, lane, ma < n, ma, enc_a, f32x4{sa.x, sa.y, sa.z, sa.w}, density_scale, sigma, rgb);
-    if (pair * 2 + 1 < n_tiles)
-      pair_tile_mlp(wl, lane, mb < n, mb, enc_b, f32x4{sb.x, sb.y, sb.z, sb.w}, density_scale, sigma, rgb);
+    pair_mlp(wl, lane, ma < n, mb < n, ma, mb, enc_a, enc_b, f32x4{sa.x, sa.y, sa.z, sa.w}, f32x4{sb.x, sb.y, sb.z, sb.w},
+             density_scale, sigma, rgb);
   }
 }
 
