@@ -61,7 +61,33 @@ class _LinearFn(torch.autograd.Function):
         return gx, gw
 
 
-_before_scatter = {}      # {"hook": callable}: called once, right before the next table-gradient scatter is queued
+class before_scatter:
+    """``with before_scatter(hook) as fork:`` - ``hook`` is called once, right before the next table-gradient scatter
+    is queued inside the block (``_table_backward``); ``fork.fired`` says whether that happened.  Leaving the block
+    removes a hook that did not fire, also on an exception.  One at a time, process-wide."""
+    pending = None
+
+    def __init__(self, hook):
+        self.hook, self.fired = hook, False
+
+    def __enter__(self):
+        if before_scatter.pending is not None:
+            raise RuntimeError("before_scatter: another hook is still waiting for its scatter")
+        before_scatter.pending = self
+        return self
+
+    def __exit__(self, *exc):
+        if before_scatter.pending is self:
+            before_scatter.pending = None
+
+    @staticmethod
+    def take():
+        """Calls the pending hook, if there is one; it is no longer pending from then on."""
+        fork = before_scatter.pending
+        if fork is not None:
+            before_scatter.pending = None
+            fork.fired = True
+            fork.hook()
 
 
 # Fixed-point table-gradient scatter (round 6; include/inr.h "Fixed-point form of the table-gradient scatter"): OPT-IN,
@@ -118,11 +144,9 @@ def _table_backward(lib, x, denc, desc, M, bound, g_emb, emb):
     the buffer is half reduced (tests/test_gpu_ddp.py caught exactly that: one run in three diverged)."""
     from .utils import grad_sync
     L = int(desc.num_levels)
-    hook = _before_scatter.pop("hook", None)
-    if hook is not None:
-        hook()      # Trainer's look-ahead: the next batch's march goes on a side stream right beside THIS launch (the
-        #             scatter is bound by the memory-side atomic unit and leaves the CUs idle; the MFMA-bound kernels
-        #             before it do not)
+    before_scatter.take()       # Trainer's look-ahead: the next batch's march goes on a side stream right beside THIS
+    #                             launch (the scatter is bound by the memory-side atomic unit and leaves the CUs idle;
+    #                             the MFMA-bound kernels before it do not)
     if grad_sync.active() and emb.data_ptr() in grad_sync.early:
         # a second backward before allreduce_gradients(): the first gradient is already being summed over the ranks,
         # adding an unreduced one to it cannot be reduced correctly afterwards

@@ -15,6 +15,7 @@ import torch
 import torch.distributed as dist
 
 from .. import _lib
+from .captured import CapturedStep, HeldCapacity, StepPipeline, copy_tensors, graph_key  # noqa: F401
 
 
 _PATCH_INDS = {}
@@ -751,26 +752,6 @@ class ParamEMA:
             s.copy_(v.to(s.device))
 
 
-def copy_tensors(pairs):
-    """[(dst, src)] device tensors of equal size: ONE launch for up to 8 of them (``inr_copy_multi``) when they are
-    contiguous GPU tensors of the same dtype with 4-byte-multiple sizes, ``dst.copy_(src)`` otherwise."""
-    import ctypes
-    fast = [(d, s) for d, s in pairs if d.is_cuda and s.is_cuda and d.dtype == s.dtype and d.is_contiguous()
-            and s.is_contiguous() and d.numel() == s.numel() and (d.numel() * d.element_size()) % 4 == 0
-            and d.device == s.device and d.data_ptr() % 4 == 0 and s.data_ptr() % 4 == 0]
-    for d, s in pairs:
-        if not any(d is f[0] for f in fast):
-            d.copy_(s, non_blocking=True)
-    lib = _lib.load()
-    for i in range(0, len(fast), 8):
-        chunk = fast[i:i + 8]
-        n = len(chunk)
-        _lib.check(lib.inr_copy_multi(n, (ctypes.c_void_p * n)(*[d.data_ptr() for d, _ in chunk]),
-                                      (ctypes.c_void_p * n)(*[s.data_ptr() for _, s in chunk]),
-                                      (ctypes.c_int64 * n)(*[d.numel() * d.element_size() for d, _ in chunk]),
-                                      _lib.stream_ptr()), "copy_multi")
-
-
 class Trainer:
     """Counterpart of upstream's ``Trainer`` (``nerf/utils.py`` of the un-vendored submodule) for the two stages the
     reference runs: NeRF training (MSE on rgb) and instance-field training (NeRF frozen,
@@ -886,8 +867,9 @@ class Trainer:
         if self.ema is not None and isinstance(self.optimizer, FusedAdam):
             self.optimizer.attach_ema(self.ema)        # the average advances inside the optimiser's launch (eager and
             #                                            captured steps: inr_adam_ema_step_multi / _dev)
-        self._graph = None
-        self._pipe = None                              # captured two-stream pipeline (use_graph and look_ahead)
+        self._graph = None                             # captured.CapturedStep (use_graph)
+        self._pipe = None                              # captured.StepPipeline (use_graph and look_ahead)
+        self._capacity = HeldCapacity()                # the captured steps' sample-buffer size: outlives load_checkpoint
         self.global_step = 0
         self.local_step = 0
         self.epoch = 0
@@ -1088,88 +1070,7 @@ class Trainer:
         return data, out
 
     # -- loops -------------------------------------------------------------------------------
-    # -- captured step ----------------------------------------------------------------------
-    GRAPH_ALIGN = 16384        # buffer sizes are rounded up to this many samples so that a graph survives the
-                               # small changes of mean_count at every occupancy update
-
-    def _graph_capacity(self, mean_count):
-        """Sample-buffer size of the captured step for a measured ``mean_count``: rounded up to GRAPH_ALIGN, and the size
-        already captured for is kept while it still holds the batch and is at most max(2 units, 1/8) too large - the
-        16-step mean of a converged scene wanders by a few thousand samples, and every change of the size is a new set
-        of graphs (tools/pipeline_convergence_probe.py: without the hold, 84 captures in 31 updates)."""
-        a = self.GRAPH_ALIGN
-        need = (mean_count + a - 1) // a * a
-        held = getattr(self, "_held_capacity", 0)
-        if need <= held <= need + max(2 * a, need // 8):
-            need = held
-        self._held_capacity = need
-        return need
-
-    def _graph_key(self, data):
-        return (self.model.mean_count, self.stage) + tuple((k, tuple(v.shape)) for k, v in sorted(data.items())
-                                                            if torch.is_tensor(v))
-
-    def _prepare_capture(self, device):
-        """Moments, fixed-point gradient state and the hyper-parameter tensor must exist BEFORE a capture (an allocation
-        + zero fill inside it would be replayed every step)."""
-        from . import network as _network
-        opt = self.optimizer
-        for g in opt.param_groups:
-            for p in g["params"]:
-                if p.requires_grad:
-                    opt._moments(p)
-                    if getattr(p, "_is_hash_table", False):
-                        _network.fx_state(p)
-                        if _network.fx_bits() == 64:
-                            _network.fx_acc64(p)
-        opt.hyper_tensor(device)
-
-    def _replay_step(self, graph, written):
-        """Replays one captured step with the host bookkeeping around it.  ``written``: the counter the graph's march
-        wrote, copied to the renderer's ``step_counter`` slot of this step; None when the total is there already."""
-        m = self.model
-        self._lr_step()
-        self.optimizer.refresh_hyper()
-        graph.replay()
-        if written is not None:
-            m.step_counter[m.local_step % 16].copy_(written)
-        m.local_step += 1
-        self.optimizer.bump_versions()
-        if self.ema is not None:
-            self.ema.update()
-
-    def _capture(self, data):
-        m = self.model
-        static = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data.items()}
-        slot = m.local_step % 16
-        self._prepare_capture(self.device)
-        self.optimizer.zero_grad()
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            _, _, loss = self.train_step(static)
-            loss.backward()
-            self.optimizer.step_captured()
-        m.local_step -= 1                       # the capture pass launched nothing; undo its bookkeeping
-        self._graph = {"graph": g, "static": static, "loss": loss, "slot": slot, "key": self._graph_key(data)}
-
-    def _replay(self, data):
-        G, m = self._graph, self.model
-        copy_tensors([(G["static"][k], v) for k, v in data.items() if torch.is_tensor(v)])
-        # the graph always writes the slot it was captured with
-        self._replay_step(G["graph"], m.step_counter[G["slot"]] if m.local_step % 16 != G["slot"] else None)
-        return G["loss"].detach()
-
-    # -- captured two-stream pipeline (use_graph and look_ahead) -------------------------------------------------
-    # The step is bound by the table-gradient scatter (memory-side atomic unit; the CUs idle for most of it) and by the
-    # host (0.6-0.85 ms to enqueue 0.83 ms of kernels; a second queue costs the runtime ~0.3 ms more per step,
-    # profiles/r03_NOTES.txt 16).  Both at once: ONE hipGraph per step holds the step's own launches on the capture
-    # stream and, forked off right before the scatter, the parameter-independent head of the NEXT batch on a second
-    # stream - ray/box test, march and, in the instance stage, the frozen NeRF's forward and the weight compositing
-    # (``NeRFRenderer.march_ahead(shade=True)``) - joined again before the graph ends.  Two persistent buffer sets
-    # alternate (step i reads set A and fills B, step i+1 reads B and fills A), so there is one graph per (set, does the
-    # step compute its own head, does it look ahead): the first step after an occupancy update computes its own head
-    # (the grid changed), the last one before an update does not look ahead.
+    # -- captured steps (nerf/captured.py) -----------------------------------------------------
     def _pipe_applies(self, data):
         m = self.model
         if not (self.use_graph and self.look_ahead and m.cuda_ray and m.mean_count > 0 and data["rays_o"].is_cuda
@@ -1191,109 +1092,15 @@ class Trainer:
         """The labels whose ignored rays the march leaves out (instance stage, ``prune_ignored``), or None."""
         return data["masks"] if (self.stage == "instance" and self.prune_ignored and "masks" in data) else None
 
-    def _pipe_init(self, data):
-        from .. import raymarching
-        m, dev = self.model, data["rays_o"].device
-        N = data["rays_o"].numel() // 3
-        M_al = raymarching.sample_capacity(m.mean_count)
-        shade = self.stage == "instance" and self.shade_ahead and m.shade_ahead_applies()
-        sets = []
-        for _ in range(2):
-            sets.append({"bufs": raymarching.march_train_buffers(N, M_al, dev, shade=shade),
-                         "static": {k: (v.clone() if torch.is_tensor(v) else v) for k, v in data.items()},
-                         "counter": torch.zeros(2, dtype=torch.int32, device=dev), "marched": None})
-        self._prepare_capture(dev)
-        self._pipe = {"key": self._graph_key(data), "sets": sets, "graphs": {}, "turn": 0, "primed": False,
-                      "expect": None, "side": torch.cuda.Stream(device=dev)}
+    def captured_graph_kinds(self):
+        """The sorted ``(prime, ahead)`` pairs - own head or prefetched, with or without look-ahead - of the graphs the
+        two-stream pipeline holds, one entry per graph; None while there is no pipeline."""
+        return None if self._pipe is None else sorted(k[1:] for k in self._pipe.graphs)
 
-    def _pipe_capture(self, turn, prime, ahead):
-        from . import network as _network
-        P, m = self._pipe, self.model
-        S, Nx = P["sets"][turn], P["sets"][turn ^ 1]
-        args = self._pipe_args()
-        if not prime and S["marched"] is None:
-            raise RuntimeError("pipeline: a step that consumes a prefetched head was asked for before any prefetch")
-        self.optimizer.zero_grad()
-        torch.cuda.synchronize()
-        step0 = m.local_step
-        side = P["side"]
-        g = torch.cuda.CUDAGraph()
-        try:
-            self._pipe_capture_body(g, S, Nx, side, prime, ahead, args)
-        finally:
-            _network._before_scatter.pop("hook", None)       # a failed capture must not leave its fork for an eager backward
-            self._ahead = None
-            m.local_step = step0                # the capture pass launched nothing; undo its bookkeeping
-        G = {"graph": g, "loss": self._pipe_loss}
-        P["graphs"][(turn, prime, ahead)] = G
-        return G
-
-    def _pipe_capture_body(self, g, S, Nx, side, prime, ahead, args):
-        from . import network as _network
-        from .. import raymarching
-        m = self.model
-        with torch.cuda.graph(g):
-            if prime:
-                S["marched"] = m.march_ahead(S["static"]["rays_o"], S["static"]["rays_d"], stream=None, bufs=S["bufs"],
-                                             counter=S["counter"], skip_labels=self._skip_labels(S["static"]), **args)
-                if S["marched"] is None:
-                    raise RuntimeError("pipeline: march_ahead refused the batch (not the steady state / staged marcher)")
-            # same graph or an earlier replay on the same stream: ordered already
-            # (the head may come from an earlier capture; whether the buffers' CONTENT is current is _pipe_step's business
-            # at every replay, so the renderer's own staleness check must not refuse it while the graph is captured)
-            self._ahead = S["marched"].ordered_here(getattr(m, "iter_density", 0))
-
-            def hook():
-                Nx["marched"] = m.march_ahead(Nx["static"]["rays_o"], Nx["static"]["rays_d"], stream=side, bufs=Nx["bufs"],
-                                              counter=Nx["counter"], skip_labels=self._skip_labels(Nx["static"]), **args)
-            if ahead and self.pipe_fork == "start":
-                hook()                               # fork right away: beside the whole step
-            elif ahead:
-                _network._before_scatter["hook"] = hook      # fork from inside the backward, right before the scatter
-            _, _, loss = self.train_step(S["static"])
-            if self._ahead is not None:
-                raise RuntimeError("pipeline: the render did not take the prefetched head")
-            loss.backward(gradient=raymarching.unit_gradient(loss.device))
-            if ahead and _network._before_scatter.pop("hook", None) is not None:
-                hook()                               # no fused table backward ran (composable path): fork here
-            self.optimizer.step_captured()
-            if ahead:
-                torch.cuda.current_stream().wait_stream(side)        # join: the graph ends with both branches done
-        self._pipe_loss = loss
-
-    def _pipe_step(self, data, next_data):
-        m = self.model
-        key = self._graph_key(data)
-        if self._pipe is None or self._pipe["key"] != key:
-            self._pipe_init(data)
-        P = self._pipe
-        t = P["turn"]
-        S, Nx = P["sets"][t], P["sets"][t ^ 1]
-        # the prefetched head is this batch's only if it was marched for these tensors through the occupancy grid as it is
-        # NOW (an update between the two steps - the trainer's own never falls there, a caller's may - bumps iter_density)
-        prime = not (P["primed"] and P["expect"] is data["rays_o"] and P.get("grid_state") == getattr(m, "iter_density", 0))
-        pairs = []
-        if prime:
-            pairs += [(S["static"][k], v) for k, v in data.items() if torch.is_tensor(v)]
-        # no look-ahead across an occupancy update (global_step is already advanced: the next call starts with one
-        # when it is a multiple of the interval), nor into a batch of another shape
-        ahead = (next_data is not None and self.global_step % self.update_extra_interval != 0
-                 and all(torch.is_tensor(next_data.get(k)) and next_data[k].shape == v.shape and next_data[k].dtype == v.dtype
-                         for k, v in Nx["static"].items() if torch.is_tensor(v)))
-        if ahead:
-            pairs += [(Nx["static"][k], v) for k, v in next_data.items() if torch.is_tensor(v)]
-        if not prime:
-            # the march of THIS batch ran in the previous replay, into the set's own counter: it goes to the renderer's
-            # slot together with the inputs (one launch); a step that marches itself copies after its replay
-            pairs.append((m.step_counter[m.local_step % 16], S["counter"]))
-        G = P["graphs"].get((t, prime, ahead)) or self._pipe_capture(t, prime, ahead)
-        copy_tensors(pairs)
-        self._replay_step(G["graph"], S["counter"] if prime else None)
-        m.last_counter = S["counter"]
-        P["primed"], P["expect"] = ahead, (next_data["rays_o"] if ahead else None)
-        P["grid_state"] = getattr(m, "iter_density", 0)
-        P["turn"] = t ^ 1
-        return G["loss"].detach()
+    def graph_captures(self):
+        """How many graphs the two-stream pipeline captured since the trainer was built or a checkpoint was loaded,
+        re-captures after a change of the buffer size included."""
+        return 0 if self._pipe is None else self._pipe.captures
 
     def _march_ahead(self, next_data):
         """Queues the march of the NEXT batch on a side stream (``NeRFRenderer.march_ahead``): it does not depend on the
@@ -1320,26 +1127,28 @@ class Trainer:
         if self.model.cuda_ray and self.global_step % self.update_extra_interval == 0:
             self.model.update_extra_state()
             if self.use_graph and self.model.mean_count > 0:
-                self.model.mean_count = self._graph_capacity(self.model.mean_count)
+                self.model.mean_count = self._capacity.fit(self.model.mean_count)
         self.global_step += 1
         if self._pipe_applies(data):
-            return self._pipe_step(data, next_data)
+            if self._pipe is None or self._pipe.key != graph_key(self.model.mean_count, self.stage, data):
+                self._pipe = StepPipeline.allocate(self, data, self._pipe.captures if self._pipe is not None else 0)
+            return self._pipe.step(data, next_data)
         if self.use_graph and self.model.cuda_ray and self.model.mean_count > 0:
-            if self._graph is None or self._graph["key"] != self._graph_key(data):
-                self._capture(data)
-            return self._replay(data)
+            if self._graph is None or self._graph.key != graph_key(self.model.mean_count, self.stage, data):
+                self._graph = CapturedStep.capture(self, data)
+            return self._graph.replay(data)
         self.optimizer.zero_grad()
         _, _, loss = self.train_step(data)
         from . import network as _network
-        if next_data is not None:
-            # queued from inside the backward, right before the table-gradient scatter (nerf/network.py::_table_backward)
-            _network._before_scatter["hook"] = lambda: self._march_ahead(next_data)
-        if loss.is_cuda and loss.dim() == 0 and loss.dtype == torch.float32:
-            from .. import raymarching
-            loss.backward(gradient=raymarching.unit_gradient(loss.device))     # no ones_like fill launch
-        else:
-            loss.backward()
-        if _network._before_scatter.pop("hook", None) is not None:
+        # the next batch's march is queued from inside the backward, right before the table-gradient scatter
+        # (nerf/network.py::_table_backward)
+        with _network.before_scatter(lambda: self._march_ahead(next_data)) as fork:
+            if loss.is_cuda and loss.dim() == 0 and loss.dtype == torch.float32:
+                from .. import raymarching
+                loss.backward(gradient=raymarching.unit_gradient(loss.device))     # no ones_like fill launch
+            else:
+                loss.backward()
+        if not fork.fired:
             self._march_ahead(next_data)            # no fused table backward ran (composable path): queue it now
         params = [p for g in self.optimizer.param_groups for p in g["params"]]
         fused = isinstance(self.optimizer, FusedAdam)

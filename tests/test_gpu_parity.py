@@ -2999,7 +2999,7 @@ def test_pipelined_captured_step_equals_eager(stage, fx_grad):
             losses.append(float(tr.train_one_step(batches[i], batches[i + 1])) if piped
                           else float(tr.train_one_step(batches[i])))
             totals.append(int(net.last_counter[0]))
-        kinds = sorted(k[1:] for k in tr._pipe["graphs"]) if piped else None
+        kinds = tr.captured_graph_kinds() if piped else None
         runs[piped] = (losses, totals, [p.detach().clone() for g in tr.optimizer.param_groups for p in g["params"]],
                        [s.clone() for s in tr.ema.shadow], tr.optimizer.step_count, net.local_step, kinds)
     a, b = runs[False], runs[True]

@@ -299,8 +299,9 @@ def train_probe(dev, rank=0, world=1, red_dev=None, steps=20, warmup=5, stage="i
             "ms_per_step_of_both_timed_regions": [round(r[0] / steps * 1e3, 3) for r in regions],
             "mode": ("pipelined: one hipGraph per step, next batch's head on a second stream inside it" if piped else
                      "eager: upstream's loop, one stream"),
-            "graphs_captured": (sorted("own head" * k[1] + "prefetched head" * (not k[1]) + " + look-ahead" * k[2]
-                                       for k in tr._pipe["graphs"]) if piped and tr._pipe else None),
+            "graphs_captured": (sorted("own head" * prime + "prefetched head" * (not prime) + " + look-ahead" * ahead
+                                       for prime, ahead in tr.captured_graph_kinds())
+                                if piped and tr.captured_graph_kinds() is not None else None),
             "loss_first": round(first, 4), "loss_last": round(float(last), 4)}
 
 
@@ -811,7 +812,7 @@ def train_loop_probe(dev, scene, stage, state, K=16, min_steps=240):
                          "vs_premade_batches": round(dt_pre / dt, 4),
                          "loss_last_epoch": round(float(tr.stats["loss"][-1]), 5)}
             if piped:
-                out[mode]["graphs_captured"] = len(tr._pipe["graphs"]) if tr._pipe else 0
+                out[mode]["graphs_captured"] = len(tr.captured_graph_kinds() or ())
         except Exception as e:                                    # noqa: BLE001
             out[mode] = {"error": f"{type(e).__name__}: {e}"[:300]}
     return out

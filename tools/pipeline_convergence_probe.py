@@ -40,14 +40,6 @@ def run(stage, pipelined, batches, init):
                  use_graph=pipelined, look_ahead=pipelined, **kw)
     if stage == "instance":
         tr.global_step = 1
-    captures = [0]
-    if pipelined:
-        inner = tr._pipe_capture
-
-        def counted(*a, **k):
-            captures[0] += 1
-            return inner(*a, **k)
-        tr._pipe_capture = counted
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     first = last = None
@@ -56,7 +48,7 @@ def run(stage, pipelined, batches, init):
     for i in range(STEPS):
         if i == tail:
             torch.cuda.synchronize()
-            t1, cap1 = time.perf_counter(), captures[0]
+            t1, cap1 = time.perf_counter(), tr.graph_captures()
         nxt = batches[i + 1] if pipelined and i + 1 < STEPS else None
         loss = tr.train_one_step(batches[i], nxt)
         if i == 0:
@@ -70,9 +62,9 @@ def run(stage, pipelined, batches, init):
     return net, tr, {"seconds": round(t2 - t0, 2), "ms_per_step": round((t2 - t0) / STEPS * 1e3, 3),
                      "ms_per_step_last_third": round((t2 - t1) / (STEPS - tail) * 1e3, 3),
                      "samples_per_step_last_third": int(n_dev) // (STEPS - tail),
-                     "graph_captures": captures[0], "graph_captures_last_third": captures[0] - cap1,
+                     "graph_captures": tr.graph_captures(), "graph_captures_last_third": tr.graph_captures() - cap1,
                      "loss_first": round(first, 4), "loss_last": round(last, 5),
-                     "pipeline_used": bool(getattr(tr, "_pipe", None))}
+                     "pipeline_used": tr.captured_graph_kinds() is not None}
 
 
 def main():

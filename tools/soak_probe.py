@@ -73,7 +73,7 @@ torch.cuda.synchronize()
 dt = time.perf_counter() - t0
 _, miou = held_out()
 print(f"instance stage: {ti.global_step - 1} steps in {dt:.1f} s = {(ti.global_step - 1) / dt:.0f} steps/s (captured two-stream pipeline, "
-      f"{len(ti._pipe['graphs']) if ti._pipe else 0} graphs), CE {ti.stats['loss'][0]:.4f} -> {ti.stats['loss'][-1]:.5f}, "
+      f"{len(ti.captured_graph_kinds() or ())} graphs), CE {ti.stats['loss'][0]:.4f} -> {ti.stats['loss'][-1]:.5f}, "
       f"NaN steps {sum(ti.stats['nan_steps'])}, held-out mIoU {miou:.3f}, parameters finite "
       f"{all(bool(torch.isfinite(p).all()) for p in net.parameters())}, peak memory {torch.cuda.max_memory_allocated() / 2 ** 30:.2f} GiB"
       + counters(net.instance_encoder.embeddings))
