@@ -400,6 +400,48 @@ int inr_grid_encode_backward_levels_fx64(const float* x, const float* grad_out, 
 int inr_grid_grad_finish_fx64(int64_t* acc64, float* grad_embeddings, const inr_grid_desc* desc /*host*/, int32_t level_lo,
                               int32_t level_hi, float* fx_state, inr_stream_t s);
 
+/* ---- 2-D hash grid (upstream's encoder_bg: get_encoder("hashgrid", input_dim=2, ...)) ----------------------------
+ * The 3-D arithmetic minus an axis, with the same descriptor (it carries no dimension; its `hashed` flags come from
+ * level_table(input_dim=2): a level is hashed iff (res+1)^2 > rows).  x [M,2] in [-bound, bound]:
+ * x01 = (x + bound) / (2 bound); out of range on either axis (NaN included) -> zero features, no gradient;
+ * pos = x01 * scale + 0.5 (separate multiply and add); corner k = 0..3, bit d of k = the +1 neighbour on axis d, weight
+ * wx * wy, features accumulated in corner order; dense row cx + cy (res+1), hashed row (cx ^ cy 2654435761u) & (rows-1).
+ * Backward: fp32 atomics into an ACCUMULATED grad_embeddings (the caller zeroes it); no input gradient (sphere
+ * coordinates never require grad) and no fixed-point form.  out / grad_out [M, 2 L], 8-byte aligned.               */
+int inr_grid2d_encode_forward(const float* x /*[M,2]*/, const float* embeddings, const inr_grid_desc* desc /*host*/,
+                              int64_t M, float bound, float* out, inr_stream_t s);
+int inr_grid2d_encode_backward(const float* x /*[M,2]*/, const float* grad_out, const inr_grid_desc* desc /*host*/,
+                               int64_t M, float bound, float* grad_embeddings, inr_stream_t s);
+
+/* ---- Background sphere model (upstream's bg_radius > 0; csrc/background.hip) -------------------------------------
+ * inr_sph_from_ray: coords [N,2] (8-byte aligned) = where the ray leaves the sphere |p| = radius (the larger root), y up,
+ * as (2 theta / pi - 1, phi / pi), in the operation order of raymarching.sph_from_ray, then clamped to [-1, 1] (NaN stays
+ * NaN).  A ray that never meets the sphere (negative discriminant, or the exit point behind the origin) gets NaN
+ * coordinates - for the 2-D grid that means zero features.
+ *
+ * inr_background_forward: bg [N,3] = sigmoid(w1 relu(w0 [sh4(rays_d), grid2d(coords)])) in ONE launch, one ray per lane:
+ * embeddings / desc = a 4-level 2-D table read with bound 1 (8 features), w0 [64,24] and w1 [3,64] row-major fp32 (SH
+ * columns first), fp32 FMAs in a fixed order.  coords_out (nullable, [N,2], 8-byte aligned) receives the coordinates,
+ * bit-equal to inr_sph_from_ray's.  weights_sum [N] + image [N,3] (nullable, together): image += (1 - weights_sum) * bg
+ * in place, a separate multiply and add - the background blend of an inference frame.
+ *
+ * inr_background_backward: recomputes the forward from its inputs (nothing else is saved) and, from grad_bg [N,3]:
+ * grad_embeddings += the table gradient (fp32 atomics, 16 rows per ray; the caller zeroes it), grad_w0 [64,24] and
+ * grad_w1 [3,64] WRITTEN (not accumulated).  The weight gradients are per-workgroup partial sums in `workspace`
+ * (inr_background_workspace_bytes(N) bytes; INR_EINVAL for a negative N) added in workgroup order by a second tiny launch
+ * inside the same call: the same inputs give the same bits.  N = 0 is valid and launches nothing (nothing is written). */
+int inr_sph_from_ray(const float* rays_o /*[N,3]*/, const float* rays_d /*[N,3]*/, int64_t N, float radius,
+                     float* coords /*[N,2]*/, inr_stream_t s);
+int inr_background_forward(const float* rays_o, const float* rays_d, int64_t N, float radius, const float* embeddings,
+                           const inr_grid_desc* desc /*host*/, const float* w0, const float* w1, float* bg,
+                           float* coords_out /*nullable*/, const float* weights_sum /*nullable*/,
+                           float* image /*nullable*/, inr_stream_t s);
+int64_t inr_background_workspace_bytes(int64_t N);
+int inr_background_backward(const float* grad_bg, const float* rays_o, const float* rays_d, int64_t N, float radius,
+                            const float* embeddings, const inr_grid_desc* desc /*host*/, const float* w0,
+                            const float* w1, float* grad_embeddings, float* grad_w0, float* grad_w1, float* workspace,
+                            inr_stream_t s);
+
 /* ---- SH (replaces shencoder sh_encode_forward / _backward, a10) ------------------------ */
 int inr_sh_encode_forward(const float* d /*[M,3]*/, int64_t M, int32_t degree, float* out, inr_stream_t s);
 int inr_sh_encode_backward(const float* grad_out, const float* d, int64_t M, int32_t degree,

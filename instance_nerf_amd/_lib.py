@@ -165,6 +165,12 @@ _SIGS = {
     "inr_linear_wgrad_workspace_bytes": (c_int64, []),
     "inr_linear_wgrad": (c_int32, [P, P, c_int64, c_int32, c_int32, P, P, P]),
     "inr_adam_step": (c_int32, [P, P, P, P, c_int64, c_float, c_float, c_float, c_float, c_int32, c_float, P]),
+    "inr_grid2d_encode_forward": (c_int32, [P, P, POINTER(GridDesc), c_int64, c_float, P, P]),
+    "inr_grid2d_encode_backward": (c_int32, [P, P, POINTER(GridDesc), c_int64, c_float, P, P]),
+    "inr_sph_from_ray": (c_int32, [P, P, c_int64, c_float, P, P]),
+    "inr_background_forward": (c_int32, [P, P, c_int64, c_float, P, POINTER(GridDesc), P, P, P, P, P, P, P]),
+    "inr_background_workspace_bytes": (c_int64, [c_int64]),
+    "inr_background_backward": (c_int32, [P, P, P, c_int64, c_float, P, POINTER(GridDesc), P, P, P, P, P, P, P]),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -310,6 +310,38 @@ __global__ void __launch_bounds__(256) k_grid_bwd_input(const float* __restrict_
   if (l == 0 && m < M) { gx[m * 3 + 0] = g0; gx[m * 3 + 1] = g1; gx[m * 3 + 2] = g2; }
 }
 
+// ---- 2-D grid (the background sphere model's encoder; grid_common.h "the 2-D grid") ---------------------------------
+// One lane per (sample, level), as k_grid_fwd.
+__global__ void __launch_bounds__(256) k_grid2d_fwd(const float* __restrict__ x, const float2* __restrict__ emb, GridDesc G,
+                                                    int64_t M, float bound, float2* __restrict__ out) {
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int L = G.num_levels;
+  const int64_t m = tid / L;
+  const int l = (int)(tid - m * L);
+  if (m >= M) return;
+  const float rb = 2.0f * bound;
+  const float x0 = (x[m * 2 + 0] + bound) / rb;
+  const float x1 = (x[m * 2 + 1] + bound) / rb;
+  out[m * L + l] = oob01_2d(x0, x1) ? make_float2(0.f, 0.f) : encode2_level(G, l, x0, x1, emb);
+}
+
+// One lane per (sample, level): eight fp32 atomics.  The samples are one per RAY (a few thousand per training step), so
+// none of k_grid_bwd's in-wave run merging is worth its instructions here.
+__global__ void __launch_bounds__(256) k_grid2d_bwd(const float* __restrict__ x, const float2* __restrict__ gout, GridDesc G,
+                                                    int64_t M, float bound, float* __restrict__ gemb) {
+  const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int L = G.num_levels;
+  const int64_t m = tid / L;
+  const int l = (int)(tid - m * L);
+  if (m >= M) return;
+  const float rb = 2.0f * bound;
+  const float x0 = (x[m * 2 + 0] + bound) / rb;
+  const float x1 = (x[m * 2 + 1] + bound) / rb;
+  if (oob01_2d(x0, x1)) return;
+  const float2 g = gout[m * L + l];
+  scatter2_level(G, l, x0, x1, g.x, g.y, gemb);
+}
+
 // ---- SH ------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) k_sh_fwd(const float* __restrict__ d, int64_t M, int degree,
                                                 float* __restrict__ out) {
@@ -768,6 +800,37 @@ int inr_grid_encode_backward_input(const float* x, const float* grad_out, const 
                                                                       reinterpret_cast<const float2*>(embeddings), G, M,
                                                                       bound, grad_x);
   return check_launch("grid_encode_backward_input");
+}
+
+int inr_grid2d_encode_forward(const float* x, const float* embeddings, const inr_grid_desc* desc, int64_t M, float bound,
+                              float* out, inr_stream_t s) {
+  INR_REQUIRE(M >= 0 && desc, "bad argument");
+  if (M == 0) return INR_OK;
+  INR_REQUIRE(x && embeddings && out, "null pointer");
+  INR_REQUIRE(bound > 0.0f, "bound must be positive");
+  GridDesc G;
+  int rc = make_grid_desc(desc, G);
+  if (rc) return rc;
+  INR_REQUIRE(((uintptr_t)embeddings & 7) == 0 && ((uintptr_t)out & 7) == 0, "embeddings/out must be 8-byte aligned");
+  k_grid2d_fwd<<<blocks_for(M * G.num_levels, 256), 256, 0, as_stream(s)>>>(x, reinterpret_cast<const float2*>(embeddings), G,
+                                                                            M, bound, reinterpret_cast<float2*>(out));
+  return check_launch("grid2d_encode_forward");
+}
+
+int inr_grid2d_encode_backward(const float* x, const float* grad_out, const inr_grid_desc* desc, int64_t M, float bound,
+                               float* grad_embeddings, inr_stream_t s) {
+  INR_REQUIRE(M >= 0 && desc, "bad argument");
+  if (M == 0) return INR_OK;
+  INR_REQUIRE(x && grad_out && grad_embeddings, "null pointer");
+  INR_REQUIRE(bound > 0.0f, "bound must be positive");
+  GridDesc G;
+  int rc = make_grid_desc(desc, G);
+  if (rc) return rc;
+  INR_REQUIRE(((uintptr_t)grad_out & 7) == 0, "grad_out must be 8-byte aligned");
+  INR_REQUIRE((uint64_t)desc->offsets[desc->num_levels] * 2ull < (1ull << 32), "table too large for 32-bit element offsets");
+  k_grid2d_bwd<<<blocks_for(M * G.num_levels, 256), 256, 0, as_stream(s)>>>(x, reinterpret_cast<const float2*>(grad_out), G, M,
+                                                                            bound, grad_embeddings);
+  return check_launch("grid2d_encode_backward");
 }
 
 int inr_sh_encode_forward(const float* d, int64_t M, int32_t degree, float* out, inr_stream_t s) {

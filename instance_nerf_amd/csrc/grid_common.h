@@ -80,6 +80,69 @@ __device__ __forceinline__ uint32_t corner_index(const GridDesc& G, int l, const
   return cx + cy * s + cz * s * s;
 }
 
+// ---- the 2-D grid (background sphere model): the same arithmetic minus an axis ----------------------------------
+// A level is dense when (res+1)^2 rows fit (gridencoder.level_table(input_dim=2) says so through desc->hashed).
+__device__ __forceinline__ bool oob01_2d(float x0, float x1) {
+  return !(x0 >= 0.0f && x0 <= 1.0f && x1 >= 0.0f && x1 <= 1.0f);
+}
+
+struct Cell2 {
+  uint32_t gx, gy;
+  float fx, fy;
+};
+
+__device__ __forceinline__ void locate2(const GridDesc& G, int l, float x0, float x1, Cell2& c) {
+  const float s = G.scales[l];
+  const float px = x0 * s + 0.5f, py = x1 * s + 0.5f;
+  const float flx = floorf(px), fly = floorf(py);
+  c.fx = px - flx; c.fy = py - fly;
+  c.gx = (uint32_t)flx; c.gy = (uint32_t)fly;
+}
+
+// corner k = 0..3: bit d of k selects the +1 neighbour on axis d; weight = wx*wy
+__device__ __forceinline__ float corner_weight2(const Cell2& c, int k) {
+  const float wx = (k & 1) ? c.fx : 1.0f - c.fx;
+  const float wy = (k & 2) ? c.fy : 1.0f - c.fy;
+  return wx * wy;
+}
+
+__device__ __forceinline__ uint32_t corner_index2(const GridDesc& G, int l, const Cell2& c, int k) {
+  const uint32_t cx = c.gx + (k & 1), cy = c.gy + ((k >> 1) & 1);
+  const uint32_t m = G.mask[l];
+  if (m) return (cx ^ (cy * 2654435761u)) & m;
+  return cx + cy * G.res1[l];
+}
+
+// Features of level l of a 2-D table at x01 (inside [0,1]^2), accumulated in corner order.
+__device__ __forceinline__ float2 encode2_level(const GridDesc& G, int l, float x0, float x1, const float2* __restrict__ emb) {
+  Cell2 c;
+  locate2(G, l, x0, x1, c);
+  float2 acc = make_float2(0.f, 0.f);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float w = corner_weight2(c, k);
+    const float2 v = emb[G.offsets[l] + corner_index2(G, l, c, k)];
+    acc.x = fmaf(w, v.x, acc.x);
+    acc.y = fmaf(w, v.y, acc.y);
+  }
+  return acc;
+}
+
+// Adds w_k * (g0, g1) to the four rows of level l that x01 touches (fp32 atomics; zero products are skipped).
+__device__ __forceinline__ void scatter2_level(const GridDesc& G, int l, float x0, float x1, float g0, float g1,
+                                               float* __restrict__ gemb) {
+  Cell2 c;
+  locate2(G, l, x0, x1, c);
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const float w = corner_weight2(c, k);
+    const uint32_t row = G.offsets[l] + corner_index2(G, l, c, k);
+    const float a = w * g0, b = w * g1;
+    if (a != 0.0f) atomicAdd(gemb + 2u * row, a);
+    if (b != 0.0f) atomicAdd(gemb + 2u * row + 1u, b);
+  }
+}
+
 // degree-4 real spherical harmonics
 __device__ __forceinline__ void sh4(float x, float y, float z, float* v) {
   const float xy = x * y, xz = x * z, yz = y * z, x2 = x * x, y2 = y * y, z2 = z * z;

@@ -88,12 +88,45 @@ class _GridEncode(torch.autograd.Function):
         return g_in, g_emb, None, None, None
 
 
+class _GridEncode2D(torch.autograd.Function):
+    """The 2-D table (the background model's ``encoder_bg``): forward, and the fp32-atomic table gradient.  No input
+    gradient (sphere coordinates never require grad) and no fixed-point form: ``INR_FX_GRAD`` does not reach it."""
+
+    @staticmethod
+    def forward(ctx, inputs, embeddings, desc, bound, out_dim):
+        lib = _lib.load()
+        inputs = inputs.detach().contiguous().float()
+        M = inputs.shape[0]
+        out = torch.empty(M, out_dim, dtype=torch.float32, device=inputs.device)
+        check(lib.inr_grid2d_encode_forward(ptr(inputs, torch.float32, "inputs", allow_none=M == 0),
+                                            ptr(embeddings, torch.float32, "embeddings"), desc, M, float(bound),
+                                            ptr(out, allow_none=M == 0), stream_ptr()), "grid2d_encode_forward")
+        ctx.save_for_backward(inputs, embeddings)
+        ctx.desc, ctx.bound = desc, bound
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        if ctx.needs_input_grad[0]:
+            raise RuntimeError("GridEncoder(input_dim=2): no gradient with respect to the input coordinates")
+        if not ctx.needs_input_grad[1]:
+            return None, None, None, None, None
+        lib = _lib.load()
+        inputs, embeddings = ctx.saved_tensors
+        grad = grad.contiguous().float()
+        M = inputs.shape[0]
+        g_emb = torch.zeros_like(embeddings)
+        check(lib.inr_grid2d_encode_backward(ptr(inputs, allow_none=M == 0), ptr(grad, torch.float32, "grad", allow_none=M == 0),
+                                             ctx.desc, M, float(ctx.bound), ptr(g_emb), stream_ptr()), "grid2d_encode_backward")
+        return None, g_emb, None, None, None
+
+
 class GridEncoder(nn.Module):
     def __init__(self, input_dim=3, num_levels=16, level_dim=2, per_level_scale=2, base_resolution=16,
                  log2_hashmap_size=19, desired_resolution=None, gridtype="hash", align_corners=False):
         super().__init__()
-        if input_dim != 3 or level_dim != 2 or gridtype != "hash" or align_corners:
-            raise RuntimeError("GridEncoder (HIP): only input_dim=3, level_dim=2, gridtype='hash', "
+        if input_dim not in (2, 3) or level_dim != 2 or gridtype != "hash" or align_corners:
+            raise RuntimeError("GridEncoder (HIP): only input_dim=2 or 3, level_dim=2, gridtype='hash', "
                                "align_corners=False are implemented")
         pls = None if desired_resolution is not None else per_level_scale
         self.table = level_table(num_levels, level_dim, base_resolution, log2_hashmap_size,
@@ -106,7 +139,8 @@ class GridEncoder(nn.Module):
         self.register_buffer("offsets", torch.from_numpy(self.table["offsets"].astype(np.int32)))
         self.n_params = self.table["total_rows"] * level_dim
         self.embeddings = nn.Parameter(torch.empty(self.table["total_rows"], level_dim))
-        self.embeddings._is_hash_table = True        # nerf/network.py::fx_state hangs the fixed-point gradient state here
+        if input_dim == 3:                           # (the 2-D table takes no part in the fixed-point scatter)
+            self.embeddings._is_hash_table = True    # nerf/network.py::fx_state hangs the fixed-point gradient state here
         self.desc = _lib.make_grid_desc(self.table)
         self.reset_parameters()
 
@@ -119,8 +153,8 @@ class GridEncoder(nn.Module):
                 f"per_level_scale={self.per_level_scale:.4f} params={tuple(self.embeddings.shape)}")
 
     def forward(self, inputs, bound=1):
-        """inputs [..., 3] in [-bound, bound] -> [..., L*F]."""
+        """inputs [..., input_dim] in [-bound, bound] -> [..., L*F]."""
         prefix = list(inputs.shape[:-1])
-        out = _GridEncode.apply(inputs.reshape(-1, self.input_dim), self.embeddings, self.desc, bound,
-                                self.output_dim)
+        fn = _GridEncode if self.input_dim == 3 else _GridEncode2D
+        out = fn.apply(inputs.reshape(-1, self.input_dim), self.embeddings, self.desc, bound, self.output_dim)
         return out.view(prefix + [self.output_dim])

@@ -19,6 +19,9 @@ Execution paths, all HIP:
 * grad, any other layer shape (or ``fused_*_train = False``): hand-written HIP
   encoders with the tiny MLP GEMMs left to rocBLAS through ``nn.Linear`` -
   upstream's default configuration (its ``--ff`` fused MLP is optional there too).
+
+``bg_radius > 0`` adds upstream's background sphere model (``encoder_bg``, ``bg_net``): per ray, one fused launch each
+way (``_BackgroundFn``, csrc/background.hip), or the composable ``background(x, d)`` for any other shape.
 """
 import math
 import os
@@ -470,6 +473,50 @@ class _NerfFieldFnUnfused(torch.autograd.Function):
         return None, None, g_emb, gws0, gws1, gwc0[:, :31], gwc1, gwc2[:3], None, None
 
 
+class _BackgroundFn(torch.autograd.Function):
+    """(rays_o, rays_d) -> bg [N,3] of the background sphere model in ONE launch each way (csrc/background.hip): sphere
+    coordinates, 2-D hash grid, SH-4, the two-layer MLP and the sigmoid, one ray per lane.  The backward recomputes the
+    forward from the rays (nothing else is saved): table gradient by fp32 atomics, the two weight gradients by
+    per-workgroup partial sums added in a fixed order (the same inputs give the same bits)."""
+
+    @staticmethod
+    def forward(ctx, rays_o, rays_d, emb, w0, w1, desc, radius):
+        lib = _lib.load()
+        f32 = torch.float32
+        N = rays_o.shape[0]
+        bg = torch.empty(N, 3, dtype=f32, device=rays_o.device)
+        w0c, w1c = w0.detach().contiguous(), w1.detach().contiguous()
+        if N:
+            check(lib.inr_background_forward(ptr(rays_o, f32, "rays_o"), ptr(rays_d, f32, "rays_d"), N, float(radius),
+                                             ptr(emb.detach(), f32, "embeddings"), desc, ptr(w0c, f32, "w0"),
+                                             ptr(w1c, f32, "w1"), ptr(bg), None, None, None, stream_ptr()),
+                  "background_forward")
+        ctx.save_for_backward(rays_o, rays_d, emb, w0c, w1c)
+        ctx.desc, ctx.radius = desc, radius
+        return bg
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        f32 = torch.float32
+        need = ctx.needs_input_grad[2:5]
+        if not any(need):
+            return None, None, None, None, None, None, None
+        rays_o, rays_d, emb, w0, w1 = ctx.saved_tensors
+        N = rays_o.shape[0]
+        # the launch forms all three gradients at once: each needs its buffer, whichever of them autograd asked for
+        g_emb = torch.zeros_like(emb)
+        gw0, gw1 = torch.zeros_like(w0), torch.zeros_like(w1)
+        if N:
+            g = g.contiguous().float()
+            ws = torch.empty(lib.inr_background_workspace_bytes(N) // 4, dtype=f32, device=g.device)
+            check(lib.inr_background_backward(ptr(g, f32, "grad_bg"), ptr(rays_o), ptr(rays_d), N, float(ctx.radius),
+                                              ptr(emb.detach(), f32, "embeddings"), ctx.desc, ptr(w0), ptr(w1), ptr(g_emb),
+                                              ptr(gw0), ptr(gw1), ptr(ws), stream_ptr()), "background_backward")
+        g_emb, gw0, gw1 = (g if n else None for g, n in zip((g_emb, gw0, gw1), need))
+        return None, None, g_emb, gw0, gw1, None, None
+
+
 class HipLinear(nn.Linear):
     """nn.Linear(bias=False) whose backward uses the HIP weight-gradient kernel (same parameters/state dict)."""
 
@@ -514,6 +561,18 @@ class NeRFNetwork(NeRFRenderer):
         self.num_layers_color, self.hidden_dim_color = num_layers_color, hidden_dim_color
         self.encoder_dir, self.in_dim_dir = get_encoder(encoding_dir)
         self.color_net = _mlp(self.in_dim_dir + geo_feat_dim, hidden_dim_color, 3, num_layers_color)
+        # Background sphere model (upstream's bg_radius > 0): a 4-level 2-D hash grid over the sphere coordinates of a
+        # ray's exit point + the direction encoding -> a small MLP -> rgb, which replaces the caller's bg_color
+        # (``background`` / ``background_rays``).  Upstream's names, so that its checkpoints load.
+        self._fusable_bg = False
+        if self.bg_radius > 0:
+            self.num_layers_bg, self.hidden_dim_bg = num_layers_bg, hidden_dim_bg
+            self.encoder_bg, self.in_dim_bg = get_encoder(encoding_bg, input_dim=2, num_levels=4, log2_hashmap_size=19,
+                                                          desired_resolution=2048)
+            self.bg_net = _mlp(self.in_dim_bg + self.in_dim_dir, hidden_dim_bg, 3, num_layers_bg)
+            self._fusable_bg = (encoding_bg == "hashgrid" and encoding_dir == "sphere_harmonics" and num_layers_bg == 2
+                                and hidden_dim_bg == 64 and self.in_dim_bg == 8 and self.in_dim_dir == 16)
+        self.fused_background = True         # False: background() on the composable path (2-D GridEncoder, SHEncoder, HipLinear)
         self.num_instances = int(num_instances)
         in_dim_inst = 0
         if self.num_instances:
@@ -550,6 +609,12 @@ class NeRFNetwork(NeRFRenderer):
                     ("num_instances", self.num_instances, "<= 64"), ("num_layers_instance", num_layers_instance, 3),
                     ("hidden_dim_instance", hidden_dim_instance, 64), ("encoder output", in_dim_inst, 32))
                 if not (v <= 64 if w == "<= 64" else v == w)))
+        if self.bg_radius > 0 and not self._fusable_bg:
+            why.append("background field: " + ", ".join(
+                f"{n}={v!r} (fused: {w!r})" for n, v, w in (
+                    ("encoding_bg", encoding_bg, "hashgrid"), ("encoding_dir", encoding_dir, "sphere_harmonics"),
+                    ("num_layers_bg", num_layers_bg, 2), ("hidden_dim_bg", hidden_dim_bg, 64),
+                    ("encoder_bg output", self.in_dim_bg, 8)) if v != w))
         self.unfused_reason = "; ".join(why) or None
         if self.unfused_reason and not NeRFNetwork._warned_unfused:
             NeRFNetwork._warned_unfused = True
@@ -652,7 +717,14 @@ class NeRFNetwork(NeRFRenderer):
         return torch.is_grad_enabled() and any(p.requires_grad for p in params)
 
     def _nerf_params(self):
-        return [self.encoder.embeddings] + [l.weight for l in self.sigma_net] + [l.weight for l in self.color_net]
+        return ([self.encoder.embeddings] + [l.weight for l in self.sigma_net] + [l.weight for l in self.color_net]
+                + self._bg_params())
+
+    def _bg_params(self):
+        """Parameters of the background sphere model (empty without one)."""
+        if self.bg_radius <= 0:
+            return []
+        return list(self.encoder_bg.parameters()) + [l.weight for l in self.bg_net]
 
     def _fused_nerf(self, x, d, want_rgb, want_geo, out=None):
         """``out`` = (sigma [M], rgb [M,3]): caller-owned result buffers (``march_ahead(shade=True)`` runs this on a
@@ -1004,6 +1076,51 @@ class NeRFNetwork(NeRFRenderer):
             return rgbs
         return h
 
+    def background(self, x, d):
+        """Upstream's ``background(x, d)``: x [N,2] sphere coordinates in [-1,1] (``raymarching.sph_from_ray``), d [N,3]
+        -> rgb [N,3] = sigmoid(bg_net([encoder_dir(d), encoder_bg(x)])), SH first.  The composable path (2-D
+        ``GridEncoder``, ``SHEncoder``, ``HipLinear``): any background shape, and the baseline of ``background_rays``."""
+        if self.bg_radius <= 0:
+            raise RuntimeError("background(): the network was built without a background model (bg_radius <= 0)")
+        h = torch.cat([self.encoder_dir(d), self.encoder_bg(x, bound=1)], dim=-1)
+        return torch.sigmoid(_run_mlp(self.bg_net, h))
+
+    def background_rays(self, rays_o, rays_d):
+        """rays_o, rays_d [N,3] -> rgb [N,3] of the background model: ``background(sph_from_ray(rays_o, rays_d,
+        bg_radius), rays_d)`` as ONE autograd node around the fused pair (``_BackgroundFn``), with gradients to the 2-D
+        table and the two weights.  ``fused_background = False``, a CPU tensor or a background shape other than upstream's
+        default (``unfused_reason``) takes the composable chain."""
+        if self.bg_radius <= 0:
+            raise RuntimeError("background_rays(): the network was built without a background model (bg_radius <= 0)")
+        rays_o, rays_d = rays_o.contiguous().float().view(-1, 3), rays_d.contiguous().float().view(-1, 3)
+        if not (self._fusable_bg and self.fused_background and rays_o.is_cuda):
+            from .. import raymarching
+            return self.background(raymarching.sph_from_ray(rays_o, rays_d, self.bg_radius), rays_d)
+        return _BackgroundFn.apply(rays_o.detach(), rays_d.detach(), self.encoder_bg.embeddings, self.bg_net[0].weight,
+                                   self.bg_net[1].weight, self.encoder_bg.desc, self.bg_radius)
+
+    @torch.no_grad()
+    def blend_background(self, rays_o, rays_d, weights_sum, image):
+        """Inference: ``image += (1 - weights_sum) * background_rays(rays_o, rays_d)`` in place (image [N,3], weights_sum
+        [N], this call's own buffers) - one launch on the fused path; -> the background [N,3]."""
+        rays_o, rays_d = rays_o.contiguous().float().view(-1, 3), rays_d.contiguous().float().view(-1, 3)
+        if not (self._fusable_bg and self.fused_background and rays_o.is_cuda):
+            bg = self.background_rays(rays_o, rays_d)
+            image.add_((1 - weights_sum).unsqueeze(-1) * bg)
+            return bg
+        lib = _lib.load()
+        f32 = torch.float32
+        N = rays_o.shape[0]
+        bg = torch.empty(N, 3, dtype=f32, device=rays_o.device)
+        if N:
+            check(lib.inr_background_forward(ptr(rays_o, f32, "rays_o"), ptr(rays_d, f32, "rays_d"), N, float(self.bg_radius),
+                                             ptr(self.encoder_bg.embeddings.data, f32, "embeddings"), self.encoder_bg.desc,
+                                             ptr(self.bg_net[0].weight.data.contiguous(), f32, "w0"),
+                                             ptr(self.bg_net[1].weight.data.contiguous(), f32, "w1"), ptr(bg), None,
+                                             ptr(weights_sum, f32, "weights_sum"), ptr(image, f32, "image"), stream_ptr()),
+                  "background_forward")
+        return bg
+
     def instance(self, x):
         """x [M,3] -> raw instance logits [M,K] (None when the network has no instance head)."""
         if not self.num_instances:
@@ -1110,6 +1227,9 @@ class NeRFNetwork(NeRFRenderer):
                   {"params": self.sigma_net.parameters(), "lr": lr},
                   {"params": self.encoder_dir.parameters(), "lr": lr},
                   {"params": self.color_net.parameters(), "lr": lr}]
+        if self.bg_radius > 0:
+            params += [{"params": self.encoder_bg.parameters(), "lr": lr},
+                       {"params": self.bg_net.parameters(), "lr": lr}]
         if self.num_instances:
             params += [{"params": self.instance_encoder.parameters(), "lr": lr},
                        {"params": self.instance_net.parameters(), "lr": lr}]

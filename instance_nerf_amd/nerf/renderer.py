@@ -128,9 +128,10 @@ class NeRFRenderer(nn.Module):
         self.density_scale = density_scale
         self.min_near = min_near
         self.density_thresh = density_thresh
+        # > 0: the subclass's background sphere model (``background_rays`` / ``blend_background``) REPLACES whatever
+        # ``bg_color`` a render call is given, in training and in inference - upstream's behaviour, also for the random
+        # background of an RGBA batch.
         self.bg_radius = bg_radius
-        if bg_radius > 0:
-            raise NotImplementedError("background sphere model is outside the hot path (SURVEY.md section 2)")
         aabb = torch.tensor([-bound, -bound, -bound, bound, bound, bound], dtype=torch.float32)
         self.register_buffer("aabb_train", aabb)
         self.register_buffer("aabb_infer", aabb.clone())
@@ -177,6 +178,20 @@ class NeRFRenderer(nn.Module):
 
     def instance(self, x):
         return None
+
+    # bg_radius > 0: the subclass's background model
+    def background_rays(self, rays_o, rays_d):
+        """rays [N,3] -> rgb [N,3] (an autograd tensor while the model trains)."""
+        raise NotImplementedError()
+
+    def blend_background(self, rays_o, rays_d, weights_sum, image):
+        """No-grad: ``image += (1 - weights_sum) * background`` in place; -> the background [N,3]."""
+        bg = self.background_rays(rays_o, rays_d).detach()
+        image.add_((1 - weights_sum).unsqueeze(-1) * bg)
+        return bg
+
+    def _bg_params(self):
+        return []
 
     # optional: what the render paths ask a subclass before they take its fused kernels (``NeRFNetwork`` sets them)
     num_instances = 0          # channels of the instance head; 0: none
@@ -256,7 +271,9 @@ class NeRFRenderer(nn.Module):
         weights_sum = weights.sum(dim=-1)
         depth = torch.sum(weights * ((z_vals - nears) / (fars - nears)).clamp(0, 1), dim=-1)
         image = torch.sum(weights.unsqueeze(-1) * rgbs, dim=-2)
-        if bg_color is None:
+        if self.bg_radius > 0:
+            bg_color = self.background_rays(rays_o, rays_d)
+        elif bg_color is None:
             bg_color = 1
         image = image + (1 - weights_sum).unsqueeze(-1) * bg_color
         results = {"image": image.view(*prefix, 3), "depth": depth.view(*prefix), "weights_sum": weights_sum.view(*prefix)}
@@ -344,6 +361,21 @@ class NeRFRenderer(nn.Module):
         else:
             raise ValueError(f"unknown infer_mode {infer_mode!r}")
         one_pass = not self.training and infer_mode != "wavefront"
+        if self.bg_radius > 0:
+            # The model's background replaces the caller's bg_color.  Where a gradient flows (to the background model,
+            # or through the shaded image) it is a per-ray tensor and the blend is _finish_rays' tensor expression;
+            # otherwise _finish_rays runs with a zero triplet and the background launch blends in place: two launches.
+            bg_flows = torch.is_grad_enabled() and any(p.requires_grad for p in self._bg_params())
+            if bg_flows or (torch.is_grad_enabled() and (image.requires_grad or weights_sum.requires_grad)):
+                with torch.set_grad_enabled(bg_flows):
+                    bg = self.background_rays(rays_o, rays_d)
+                return self._finish_rays(results, prefix, weights_sum, depth, image, nears, fars, bg, mse_target,
+                                         one_pass, jitter, dt_gamma, max_steps)
+            results = self._finish_rays(results, prefix, weights_sum, depth, image, nears, fars, 0, mse_target, one_pass,
+                                        jitter, dt_gamma, max_steps)
+            self.blend_background(rays_o, rays_d, results["weights_sum"].detach().reshape(-1).contiguous().float(),
+                                  results["image"].view(-1, 3))
+            return results
         return self._finish_rays(results, prefix, weights_sum, depth, image, nears, fars,
                                  1 if bg_color is None else bg_color, mse_target, one_pass, jitter, dt_gamma, max_steps)
 
@@ -552,7 +584,8 @@ class NeRFRenderer(nn.Module):
         bg3 = self._bg_triplet(bg_color)
         flows = torch.is_grad_enabled() and (image.requires_grad or weights_sum.requires_grad)
         bg_per_ray = torch.is_tensor(bg_color) and bg_color.is_cuda and bg_color.numel() == 3 * N
-        if (self.training and mse_target is not None and flows and t_start is None and image.is_cuda
+        bg_trained = torch.is_tensor(bg_color) and bg_color.requires_grad      # the fused tail gives a background no gradient
+        if (self.training and mse_target is not None and flows and t_start is None and image.is_cuda and not bg_trained
                 and 0 < N <= raymarching.FINISH_MSE_MAX_RAYS and (bg3 is not None or bg_per_ray)):
             image, depth, results["image_mse"] = raymarching.finish_rays_mse(
                 image, weights_sum, depth, nears, fars, bg3 if bg3 is not None else bg_color, mse_target)

@@ -864,6 +864,13 @@ class Trainer:
         # replayed; one process, FusedAdam only, built-in learning-rate rule.  Falls back to the eager step otherwise.
         self.use_graph = (bool(use_graph) and world_size == 1 and isinstance(self.optimizer, FusedAdam)
                           and self.lr_scheduler is None)
+        if self.use_graph and getattr(model, "bg_radius", -1) > 0:
+            # the captured step was not extended to the background model (its autograd node, the tensor blend and the
+            # host-formed loss are outside what CapturedStep records): such a model trains on the eager step
+            self.use_graph = False
+            import warnings
+            warnings.warn("Trainer: use_graph=True is not available with a background model (bg_radius > 0); "
+                          "training on the eager step", RuntimeWarning, stacklevel=2)
         if self.ema is not None and isinstance(self.optimizer, FusedAdam):
             self.optimizer.attach_ema(self.ema)        # the average advances inside the optimiser's launch (eager and
             #                                            captured steps: inr_adam_ema_step_multi / _dev)

@@ -77,8 +77,21 @@ def near_far_from_aabb(rays_o, rays_d, aabb, min_near=0.2, out=None, skip_labels
 def sph_from_ray(rays_o, rays_d, radius):
     """rays_o, rays_d [N,3], radius -> coords [N,2] in [-1,1]: where each ray leaves the sphere of that radius, as
     (2 theta / pi - 1, phi / pi) with y the up axis - upstream's ``raymarching.sph_from_ray`` [U], the input of its
-    background model (``bg_radius > 0``).  The background model itself is outside the hot path, so this
-    helper is plain tensor ops; it exists because callers written against upstream import the name."""
+    background model (``bg_radius > 0``, ``NeRFNetwork.background``).  GPU tensors: one launch (``inr_sph_from_ray``;
+    the fused background kernels call the same device function, so their coordinates have the same bits); CPU tensors:
+    the tensor ops below, the same arithmetic.  Canonical choices of this project: both
+    coordinates are clamped to [-1, 1] - in fp32 ``2 theta / pi - 1`` can land one ulp past 1 at the pole, which the grid
+    would read as "outside" -, NaN stays NaN, and a ray that never meets the sphere (negative discriminant, or the exit
+    point behind the origin) gets NaN coordinates: the 2-D grid then gives zero features."""
+    if rays_o.is_cuda:
+        lib = _lib.load()
+        prefix = rays_o.shape[:-1]
+        o, d = _f(rays_o).view(-1, 3), _f(rays_d).view(-1, 3)
+        N = o.shape[0]
+        coords = torch.empty(N, 2, dtype=F32, device=o.device)
+        check(lib.inr_sph_from_ray(ptr(o, F32, "rays_o", allow_none=N == 0), ptr(d, F32, "rays_d", allow_none=N == 0), N,
+                                   float(radius), ptr(coords, allow_none=N == 0), stream_ptr()), "sph_from_ray")
+        return coords.view(*prefix, 2)
     o, d = rays_o.float(), rays_d.float()
     A = (d * d).sum(-1)
     B = (o * d).sum(-1)                                   # in fact B / 2
@@ -87,7 +100,8 @@ def sph_from_ray(rays_o, rays_d, radius):
     p = o + t.unsqueeze(-1) * d
     theta = torch.atan2(torch.sqrt(p[..., 0] ** 2 + p[..., 2] ** 2), p[..., 1])
     phi = torch.atan2(p[..., 2], p[..., 0])
-    return torch.stack([2 * theta / math.pi - 1, phi / math.pi], -1)
+    coords = torch.stack([2 * theta / math.pi - 1, phi / math.pi], -1).clamp(-1, 1)           # (clamp keeps NaN)
+    return torch.where((t >= 0).unsqueeze(-1), coords, torch.full_like(coords, float("nan")))
 
 
 def morton3D(coords):
