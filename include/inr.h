@@ -122,6 +122,45 @@ int inr_sample_training_batch(const float* pose /*[4,4]*/, float fx, float fy, f
                               float* rays_o, float* rays_d, float* rgb /*[n,channels]*/, int64_t* labels /*[n]*/,
                               inr_stream_t s);
 
+/* The same batch with the pixels drawn from ONE image's row of a coarse error map (upstream's --error_map /
+ * opt.error_map [U]: NeRFDataset.error_map [n_images, 128*128] and get_rays(error_map=...), a torch.multinomial draw of
+ * n cells without replacement, then a uniform pixel inside each cell), still ONE launch (one workgroup; no read-back, no
+ * float atomics).  error_map float [cells*cells], 1 <= cells <= 128, n <= cells*cells.  The draw has multinomial's
+ * distribution (exponential race, Efraimidis-Spirakis: the n smallest keys E_c / w_c win) and is a function of
+ * (seed, step, cell) alone:
+ *   ctr(s, c) = 2^63 + step * 2^32 + s * 2^16 + c     stream s = 0 key, 1 row jitter, 2 column jitter (bit 63 keeps them
+ *                                                     apart from inr_sample_training_batch's counters step * 2^32 + k)
+ *   m_s(c)    = mix64(seed + 0x9E3779B97F4A7C15 * ctr(s, c)) >> 40          (24 bits)
+ *   E_c       = -ln((m_0(c) + 0.5) * 2^-24) by a fixed binary32 sequence (csrc/raymarch.hip neg_ln_u24: integer
+ *               exponent / mantissa split, s = (f-1)/(f+1), degree-4 polynomial in s*s, separate multiplies and adds;
+ *               within 1e-6 relative of the exact value for every m)
+ *   key_c     = E_c / w_c, an IEEE binary32 division; w_c <= 0 or NaN: +inf (such a cell is taken only after every
+ *               positive one, lowest index first); w_c = +inf: 0.  Keys are >= 0: their bits order as unsigned integers.
+ *   winners   = the n smallest (key bits, c) pairs - equal bits resolve to the smaller cell index.
+ * Outputs are in ASCENDING cell index: inds_coarse[k] = c (upstream's key), and the pixel by upstream's rule in binary32,
+ * every product and sum rounded on its own:
+ *   cx_ = c / cells, cy_ = c % cells, sx = (float)H / (float)cells, sy = (float)W / (float)cells,
+ *   r1 = (float)m_1(c) * 2^-24, r2 = (float)m_2(c) * 2^-24,
+ *   px = min((int)((float)cx_ * sx + r1 * sx), H - 1), py = min((int)((float)cy_ * sy + r2 * sy), W - 1),
+ *   inds[k] = px * W + py;
+ * rays, rgb and labels for inds exactly as inr_sample_training_batch (the same device code).  Restated bit for bit by
+ * tests/error_map_reference.py.                                                                                       */
+int inr_sample_training_batch_weighted(const float* pose /*[4,4]*/, float fx, float fy, float cx, float cy, int32_t H,
+                                       int32_t W, const float* image /*nullable*/, int32_t channels,
+                                       const int32_t* mask /*nullable*/, int32_t num_instances,
+                                       const float* error_map /*[cells*cells]*/, int32_t cells, int64_t seed, int64_t step,
+                                       int64_t n, int64_t* inds /*[n]*/, int64_t* inds_coarse /*[n]*/, float* rays_o,
+                                       float* rays_d, float* rgb /*[n,channels]*/, int64_t* labels /*[n]*/,
+                                       inr_stream_t s);
+/* The error map's update after a training step (upstream's Trainer.train_step [U]: error = MSELoss(reduction='none')
+ * (pred, gt).mean(-1), map[inds_coarse] = 0.1 * map[inds_coarse] + 0.9 * error), one launch: for ray k with cell
+ * c = inds_coarse[k], d = pred[k] - target[k]:  e = ((d0*d0 + d1*d1) + d2*d2) / 3.0f;  map[c] = 0.1f * map[c] + 0.9f * e
+ * (separate multiplies and adds).  pred, target float [N,3]; map float [cells*cells] (one image's row), 1 <= cells <= 128.
+ * An index outside [0, cells*cells) is skipped.  inr_sample_training_batch_weighted hands out distinct cells, so its
+ * indices never race; for a caller's own DUPLICATE indices which of the rays writes last is unspecified.              */
+int inr_error_map_update(const float* pred /*[N,3]*/, const float* target /*[N,3]*/, const int64_t* inds_coarse /*[N]*/,
+                         float* map /*[cells*cells]*/, int64_t N, int32_t cells, inr_stream_t s);
+
 int inr_near_far_from_aabb(const float* rays_o, const float* rays_d, const float* aabb /*[6]*/,
                            int64_t N, float min_near, float* nears, float* fars, inr_stream_t s);
 /* The same with per-ray labels (int64 [N]): a ray whose label equals `ignore_index` is reported as a miss (near = far =

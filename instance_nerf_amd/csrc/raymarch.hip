@@ -89,17 +89,13 @@ __device__ __forceinline__ uint64_t mix64(uint64_t z) {
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
-__global__ void __launch_bounds__(kRayBlock) k_sample_batch(const float* __restrict__ pose, float fx, float fy, float cx,
-                                                            float cy, int H, int W, const float* __restrict__ image,
-                                                            int C, const int32_t* __restrict__ mask, int num_instances,
-                                                            uint64_t seed, uint64_t step, int64_t n,
-                                                            int64_t* __restrict__ inds, float* __restrict__ rays_o,
-                                                            float* __restrict__ rays_d, float* __restrict__ rgb,
-                                                            int64_t* __restrict__ labels) {
-  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (k >= n) return;
-  const uint64_t h = mix64(seed + 0x9E3779B97F4A7C15ull * ((step << 32) + (uint64_t)k));
-  const uint64_t pix = ((h >> 32) * (uint64_t)((int64_t)H * W)) >> 32;
+// sample k = pixel `pix`: index, ray, colour, label (shared by the uniform and the error-map loader, so both carry
+// k_get_rays' bits for the same pixel)
+__device__ __forceinline__ void finish_sample(const float* __restrict__ pose, float fx, float fy, float cx, float cy, int W,
+                                              const float* __restrict__ image, int C, const int32_t* __restrict__ mask,
+                                              int num_instances, int64_t k, uint64_t pix, int64_t* __restrict__ inds,
+                                              float* __restrict__ rays_o, float* __restrict__ rays_d,
+                                              float* __restrict__ rgb, int64_t* __restrict__ labels) {
   inds[k] = (int64_t)pix;
   const float i = (float)(pix % (uint64_t)W) + 0.5f, j = (float)(pix / (uint64_t)W) + 0.5f;
   const float xs = (i - cx) / fx, ys = (j - cy) / fy;
@@ -117,6 +113,202 @@ __global__ void __launch_bounds__(kRayBlock) k_sample_batch(const float* __restr
     const int32_t l = mask[pix];
     labels[k] = l >= num_instances ? -1 : (int64_t)l;
   }
+}
+__global__ void __launch_bounds__(kRayBlock) k_sample_batch(const float* __restrict__ pose, float fx, float fy, float cx,
+                                                            float cy, int H, int W, const float* __restrict__ image,
+                                                            int C, const int32_t* __restrict__ mask, int num_instances,
+                                                            uint64_t seed, uint64_t step, int64_t n,
+                                                            int64_t* __restrict__ inds, float* __restrict__ rays_o,
+                                                            float* __restrict__ rays_d, float* __restrict__ rgb,
+                                                            int64_t* __restrict__ labels) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= n) return;
+  const uint64_t h = mix64(seed + 0x9E3779B97F4A7C15ull * ((step << 32) + (uint64_t)k));
+  const uint64_t pix = ((h >> 32) * (uint64_t)((int64_t)H * W)) >> 32;
+  finish_sample(pose, fx, fy, cx, cy, W, image, C, mask, num_instances, k, pix, inds, rays_o, rays_d, rgb, labels);
+}
+
+// ------------------------------------------------------------------------------------------
+// The same batch with the pixels drawn from a coarse error map (upstream's --error_map [U]: NeRFDataset.error_map
+// [n_images, 128*128], get_rays(error_map=...): torch.multinomial without replacement over the cells, then a uniform
+// pixel inside each cell), in ONE launch of ONE workgroup.  The weighted draw without replacement is an exponential
+// race (Efraimidis-Spirakis): cell c of a cells x cells map row gets the key E_c / w_c, the n smallest keys win - the
+// distribution of sequential sampling without replacement, i.e. of torch.multinomial(w, n, replacement=False).
+// Everything is a function of (seed, step, cell), restated bit for bit by tests/error_map_reference.py:
+//   ctr(s, c) = 2^63 + step * 2^32 + s * 2^16 + c          stream s = 0 key, 1 row jitter, 2 column jitter; bit 63
+//                                                          keeps them apart from the uniform loader's step * 2^32 + k
+//   m_s(c)    = mix64(seed + GOLDEN * ctr(s, c)) >> 40     (24 bits)
+//   E_c       = neg_ln_u24(m_0(c))  = -ln(u), u = (m + 0.5) * 2^-24, by the fp32 sequence below (no device logf)
+//   key_c     = E_c / w_c (IEEE binary32 division);  w_c <= 0 or NaN: +inf (taken only after every positive cell, lowest
+//               index first);  w_c = +inf: 0.  Keys are >= 0, so their bit patterns order as unsigned integers.
+//   winners   = the n smallest (key bits, c) pairs; written in ASCENDING c (deterministic; 16 consecutive rays are
+//               neighbours in the image).
+//   pixel of winner c:  cx_ = c / cells, cy_ = c % cells, sx = (float)H / (float)cells, sy = (float)W / (float)cells,
+//               r1 = (float)m_1(c) * 2^-24, r2 = (float)m_2(c) * 2^-24,
+//               px = min((int)((float)cx_ * sx + r1 * sx), H - 1), py = min((int)((float)cy_ * sy + r2 * sy), W - 1),
+//               pix = px * W + py     (upstream's rule, get_rays of nerf/utils.py; products and sums rounded separately)
+// then finish_sample as the uniform loader.  Shape: 1024 threads x 16 cells each (thread t owns cells 16 t .. 16 t + 15),
+// the keys stay in registers; radix select of the n-th smallest key over four 8-bit digits (256-bin integer histogram
+// in LDS, each thread merges runs of equal digits before it adds), then one packed block scan of (keys below the
+// threshold, keys equal to it) gives every thread its output offset.  No read-back, no float atomics.
+//
+// neg_ln_u24(m), m < 2^24: v = 2 m + 1 (u = v / 2^25, exact integers all the way to the quotient, so u -> 1 keeps its
+// relative accuracy);  e0 = floor(log2 v);  vn = v << (24 - e0) in [2^24, 2^25);  up = vn >= 23726566 (sqrt(2) * 2^24);
+// one = up ? 2^25 : 2^24;  a = (float)(vn - one), b = (float)(vn + one) (round to nearest even);  s = a / b
+// ((f - 1) / (f + 1) of the mantissa f in [sqrt(1/2), sqrt(2)));  z = s * s;
+// p = (((z * (1/9) + 1/7) * z + 1/5) * z + 1/3) * z + 1;  ln f = (s + s) * p;  kf = (float)(25 - e0 - up);
+// result = kf * ln2 - ln f.   Every product and sum is one binary32 operation (-ffp-contract=off).
+__device__ __forceinline__ float neg_ln_u24(uint32_t m) {
+  const uint32_t v = 2u * m + 1u;
+  const int e0 = 31 - __clz((int)v);
+  const uint32_t vn = v << (24 - e0);
+  const bool up = vn >= 23726566u;
+  const uint32_t one = up ? (1u << 25) : (1u << 24);
+  const float a = (float)((int32_t)vn - (int32_t)one), b = (float)(vn + one);
+  const float s = a / b, z = s * s;
+  float p = z * 0.11111111f + 0.14285715f;
+  p = p * z + 0.2f;
+  p = p * z + 0.33333334f;
+  p = p * z + 1.0f;
+  const float lnf = (s + s) * p;
+  const float kf = (float)(25 - e0 - (up ? 1 : 0));
+  return kf * 0.69314718f - lnf;
+}
+constexpr int kDrawBlock = 1024, kDrawPer = 16;      // 1024 * 16 = 128 * 128 cells
+__global__ void __launch_bounds__(kDrawBlock) k_sample_batch_weighted(
+    const float* __restrict__ pose, float fx, float fy, float cx, float cy, int H, int W, const float* __restrict__ image,
+    int C, const int32_t* __restrict__ mask, int num_instances, const float* __restrict__ error_map, int cells,
+    uint64_t seed, uint64_t step, int n, int64_t* __restrict__ inds, int64_t* __restrict__ inds_coarse,
+    float* __restrict__ rays_o, float* __restrict__ rays_d, float* __restrict__ rgb, int64_t* __restrict__ labels) {
+  __shared__ uint32_t hist[256];
+  __shared__ uint32_t wave_tot[kDrawBlock / 64];
+  __shared__ uint32_t sel[2];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int total = cells * cells;
+  const uint64_t base = (1ull << 63) + (step << 32);
+  constexpr uint64_t kGolden = 0x9E3779B97F4A7C15ull;
+  uint32_t key[kDrawPer];
+#pragma unroll
+  for (int j = 0; j < kDrawPer; ++j) {
+    const int c = tid * kDrawPer + j;
+    uint32_t kb = 0xFFFFFFFFu;                        // no such cell: above every key, never selected (n <= total)
+    if (c < total) {
+      const float w = error_map[c];
+      kb = 0x7F800000u;
+      if (w > 0.0f) kb = __float_as_uint(neg_ln_u24((uint32_t)(mix64(seed + kGolden * (base + (uint64_t)c)) >> 40)) / w);
+    }
+    key[j] = kb;
+  }
+  // the n-th smallest key: its bits digit by digit; `want` = its rank among the keys that share the digits found so far
+  uint32_t prefix = 0, want = (uint32_t)n;
+#pragma unroll
+  for (int pass = 0; pass < 4; ++pass) {
+    const int shift = 24 - 8 * pass;
+    if (tid < 256) hist[tid] = 0;
+    __syncthreads();
+    uint32_t run_d = 0, run_c = 0;
+#pragma unroll
+    for (int j = 0; j < kDrawPer; ++j) {
+      const bool cand = pass == 0 || (key[j] >> ((shift + 8) & 31)) == prefix;
+      const uint32_t d = (key[j] >> shift) & 255u;
+      if (cand) {
+        if (run_c != 0 && d != run_d) {
+          atomicAdd(&hist[run_d], run_c);
+          run_c = 0;
+        }
+        run_d = d;
+        ++run_c;
+      }
+    }
+    if (run_c != 0) atomicAdd(&hist[run_d], run_c);
+    __syncthreads();
+    if (wave == 0) {
+      const uint32_t c0 = hist[lane * 4], c1 = hist[lane * 4 + 1], c2 = hist[lane * 4 + 2], c3 = hist[lane * 4 + 3];
+      const uint32_t sum = c0 + c1 + c2 + c3;
+      uint32_t incl = sum;
+#pragma unroll
+      for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t t = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += t;
+      }
+      const uint32_t excl = incl - sum;
+      if (excl < want && want <= incl) {              // exactly one lane: 1 <= want <= number of candidates
+        uint32_t r = want - excl, b = 0;
+        if (r > c0) {
+          r -= c0; b = 1;
+          if (r > c1) {
+            r -= c1; b = 2;
+            if (r > c2) { r -= c2; b = 3; }
+          }
+        }
+        sel[0] = (uint32_t)lane * 4 + b;
+        sel[1] = r;
+      }
+    }
+    __syncthreads();
+    prefix = (prefix << 8) | sel[0];
+    want = sel[1];
+  }
+  // winners: every key below the threshold `prefix`, and the first `want` (by cell index) of the keys equal to it
+  uint32_t lt = 0, eq = 0;
+#pragma unroll
+  for (int j = 0; j < kDrawPer; ++j) {
+    lt += key[j] < prefix ? 1u : 0u;
+    eq += key[j] == prefix ? 1u : 0u;
+  }
+  const uint32_t packed = lt | (eq << 16);            // both totals <= 16384: the halves never carry into each other
+  uint32_t incl = packed;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const uint32_t t = __shfl_up(incl, d, 64);
+    if (lane >= d) incl += t;
+  }
+  if (lane == 63) wave_tot[wave] = incl;
+  __syncthreads();
+  uint32_t before = incl - packed;
+  for (int w = 0; w < wave; ++w) before += wave_tot[w];
+  uint32_t eq_rank = before >> 16;
+  int pos = (int)((before & 0xFFFFu) + (eq_rank < want ? eq_rank : want));
+  uint32_t winners = 0;
+#pragma unroll
+  for (int j = 0; j < kDrawPer; ++j) {
+    bool win = key[j] < prefix;
+    if (key[j] == prefix) {
+      win = eq_rank < want;
+      ++eq_rank;
+    }
+    winners |= win ? (1u << j) : 0u;
+  }
+  const float sx = (float)H / (float)cells, sy = (float)W / (float)cells;
+  while (winners != 0 && pos < n) {
+    const int c = tid * kDrawPer + (__ffs((int)winners) - 1);
+    winners &= winners - 1;
+    const float r1 = (float)(uint32_t)(mix64(seed + kGolden * (base + (1ull << 16) + (uint64_t)c)) >> 40) * 5.9604644775390625e-8f;
+    const float r2 = (float)(uint32_t)(mix64(seed + kGolden * (base + (2ull << 16) + (uint64_t)c)) >> 40) * 5.9604644775390625e-8f;
+    const int cx_ = c / cells, cy_ = c - cx_ * cells;
+    int px = (int)((float)cx_ * sx + r1 * sx), py = (int)((float)cy_ * sy + r2 * sy);
+    px = px < H - 1 ? px : H - 1;
+    py = py < W - 1 ? py : W - 1;
+    inds_coarse[pos] = (int64_t)c;
+    finish_sample(pose, fx, fy, cx, cy, W, image, C, mask, num_instances, (int64_t)pos, (uint64_t)((int64_t)px * W + py), inds,
+                  rays_o, rays_d, rgb, labels);
+    ++pos;
+  }
+}
+// upstream's Trainer.train_step with an error map [U]: error = criterion(pred, gt).mean(-1) per ray, then
+// map[inds_coarse] = 0.1 * map[inds_coarse] + 0.9 * error - one launch; an index outside the map is skipped.
+__global__ void __launch_bounds__(kRayBlock) k_error_map_update(const float* __restrict__ pred,
+                                                                const float* __restrict__ target,
+                                                                const int64_t* __restrict__ inds_coarse,
+                                                                float* __restrict__ map, int64_t N, int64_t total) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= N) return;
+  const int64_t c = inds_coarse[k];
+  if (c < 0 || c >= total) return;
+  const float d0 = pred[k * 3] - target[k * 3], d1 = pred[k * 3 + 1] - target[k * 3 + 1];
+  const float d2 = pred[k * 3 + 2] - target[k * 3 + 2];
+  const float e = ((d0 * d0 + d1 * d1) + d2 * d2) / 3.0f;
+  map[c] = 0.1f * map[c] + 0.9f * e;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1832,6 +2024,39 @@ int inr_sample_training_batch(const float* pose, float fx, float fy, float cx, f
                                                                            num_instances, (uint64_t)seed, (uint64_t)step, n,
                                                                            inds, rays_o, rays_d, rgb, labels);
   return check_launch("sample_training_batch");
+}
+
+int inr_sample_training_batch_weighted(const float* pose, float fx, float fy, float cx, float cy, int32_t H, int32_t W,
+                                       const float* image, int32_t channels, const int32_t* mask, int32_t num_instances,
+                                       const float* error_map, int32_t cells, int64_t seed, int64_t step, int64_t n,
+                                       int64_t* inds, int64_t* inds_coarse, float* rays_o, float* rays_d, float* rgb,
+                                       int64_t* labels, inr_stream_t s) {
+  INR_REQUIRE(n >= 0 && H > 0 && W > 0 && (int64_t)H * W < (1ll << 31), "bad sizes");
+  INR_REQUIRE(step >= 0 && step < (1ll << 31), "step out of range (0 .. 2^31 - 1)");
+  INR_REQUIRE(!image || channels == 3 || channels == 4, "channels must be 3 or 4");
+  INR_REQUIRE(!mask || num_instances > 0, "num_instances must be positive with a mask");
+  INR_REQUIRE(cells >= 1 && cells <= 128, "cells must be 1 .. 128");
+  INR_REQUIRE(n <= (int64_t)cells * cells, "n exceeds cells * cells (the draw is without replacement)");
+  if (n == 0) return INR_OK;
+  INR_REQUIRE(pose && error_map && inds && inds_coarse && rays_o && rays_d, "null pointer");
+  INR_REQUIRE((!image || rgb) && (!mask || labels), "null output for a given input");
+  static_assert(kDrawBlock * kDrawPer >= 128 * 128, "one workgroup holds every cell");
+  k_sample_batch_weighted<<<1, kDrawBlock, 0, as_stream(s)>>>(pose, fx, fy, cx, cy, H, W, image, channels, mask,
+                                                              num_instances, error_map, cells, (uint64_t)seed,
+                                                              (uint64_t)step, (int)n, inds, inds_coarse, rays_o, rays_d,
+                                                              rgb, labels);
+  return check_launch("sample_training_batch_weighted");
+}
+
+int inr_error_map_update(const float* pred, const float* target, const int64_t* inds_coarse, float* map, int64_t N,
+                         int32_t cells, inr_stream_t s) {
+  INR_REQUIRE(N >= 0, "negative N");
+  INR_REQUIRE(cells >= 1 && cells <= 128, "cells must be 1 .. 128");
+  if (N == 0) return INR_OK;
+  INR_REQUIRE(pred && target && inds_coarse && map, "null pointer");
+  k_error_map_update<<<blocks_for(N, kRayBlock), kRayBlock, 0, as_stream(s)>>>(pred, target, inds_coarse, map, N,
+                                                                               (int64_t)cells * cells);
+  return check_launch("error_map_update");
 }
 
 int inr_near_far_from_aabb(const float* rays_o, const float* rays_d, const float* aabb, int64_t N,

@@ -77,10 +77,16 @@ class NeRFDataset:
     ``rays_o, rays_d [1,N,3]``, ``images [1,N,3]``, ``masks [1,N]`` (if ``mask_dir``), ``H, W, index``;
     otherwise the full image in row-major order.  ``seed`` / ``rank``: the view order and the pixel draws are functions of
     ``seed + 1000 * rank`` (one process per GPU: every rank its own batches).
+    ``error_map=True`` (upstream's ``--error_map``; ``opt.error_map`` in the ``opt`` form), training datasets only: the
+    dataset owns ``error_map`` float32 ``[n_images, error_map_cells ** 2]`` of ones on ``device``; every batch draws
+    its ``num_rays`` (<= cells^2) pixels from the image's row - cells without replacement in proportion to the map, a
+    uniform pixel inside each - and carries ``inds_coarse [1,N]``; ``Trainer`` (stage "nerf") folds each step's per-ray
+    loss back into the map.  Default off: ``error_map`` is None and nothing else changes.
     """
 
     def __init__(self, path, type="train", device="cpu", downscale=1, scale=0.33, offset=(0, 0, 0), num_rays=4096,
-                 mask_dir=None, num_instances=0, preload=True, seed=0, n_test=10, rank=0):
+                 mask_dir=None, num_instances=0, preload=True, seed=0, n_test=10, rank=0, error_map=False,
+                 error_map_cells=128):
         import json
         import os
         if hasattr(path, "path"):
@@ -100,6 +106,7 @@ class NeRFDataset:
             mask_dir = getattr(opt, "mask_dir", mask_dir)
             num_instances = getattr(opt, "num_instances", num_instances)
             seed, rank = getattr(opt, "seed", seed), getattr(opt, "local_rank", rank)
+            error_map = getattr(opt, "error_map", error_map)                   # upstream's --error_map
             self.opt = opt
         self.root, self.type, self.device = path, type, torch.device(device)
         self.training = type in ("train", "all", "trainval")
@@ -177,6 +184,17 @@ class NeRFDataset:
         # rgb gather, label gather.  The draw is counter-based: batch number `_draws` of this loader under `seed`.
         self.seed, self._draws = int(seed) + 1000 * int(rank), 0
         self.fused_batches = True
+        # upstream's --error_map: a coarse per-image map of the training error (ones at first) that the pixel draw follows
+        # and Trainer.train_step updates.  Upstream keeps it on the CPU; here it sits with the batches, because the fused
+        # loader reads it (inr_sample_training_batch_weighted).  Evaluation datasets never get one.
+        self.error_map, self.error_map_cells = None, int(error_map_cells)
+        if error_map and self.training:
+            if not 1 <= self.error_map_cells <= 128:
+                raise ValueError(f"error_map_cells must be 1 .. 128, got {error_map_cells}")
+            if self.num_rays > self.error_map_cells ** 2:
+                raise ValueError(f"num_rays = {self.num_rays} exceeds the error map's {self.error_map_cells}^2 cells "
+                                 "(the cells are drawn without replacement)")
+            self.error_map = torch.ones(len(poses), self.error_map_cells ** 2, dtype=torch.float32, device=self.device)
 
     def __len__(self):
         return self.poses.shape[0]
@@ -184,8 +202,21 @@ class NeRFDataset:
     def _fused_batch(self, index):
         """One training batch in one launch (``inr_sample_training_batch``, include/inr.h): what the tensor-op path below
         does in eight launches - ``torch.randint`` draw, ``get_rays``, image gather, ``labels_for_rays`` - with the pixel
-        draw made reproducible from (seed, batch number).  Same dict, same shapes and dtypes."""
+        draw made reproducible from (seed, batch number).  Same dict, same shapes and dtypes.  With an error map the
+        launch is ``inr_sample_training_batch_weighted`` and the batch carries ``inds_coarse`` [1, n] (upstream's key)."""
         from .. import _lib
+        if self.error_map is not None:
+            from .. import raymarching
+            mask = self.masks[index] if self.masks is not None else None
+            b = raymarching.sample_training_batch_weighted(
+                self.poses[index], self.intrinsics, self.H, self.W, self.images[index], mask, self.num_instances,
+                self.error_map[index], self.error_map_cells, self.seed, self._draws & 0x7FFFFFFF, int(self.num_rays))
+            self._draws += 1
+            out = {"H": self.H, "W": self.W, "rays_o": b["rays_o"][None], "rays_d": b["rays_d"][None], "index": [index],
+                   "images": b["rgb"][None], "inds_coarse": b["inds_coarse"][None]}
+            if b["labels"] is not None:
+                out["masks"] = b["labels"][None]
+            return out
         lib = _lib.load()
         n, dev = int(self.num_rays), self.device
         C = int(self.images.shape[-1])
@@ -214,9 +245,12 @@ class NeRFDataset:
         if (self.training and self.fused_batches and self.num_rays > 0 and self.device.type == "cuda" and self.images.is_cuda
                 and self.images.dtype == torch.float32 and (self.masks is None or self.masks.is_cuda)):
             return self._fused_batch(index)
-        r = get_rays(self.poses[index:index + 1], self.intrinsics, self.H, self.W, self.num_rays)
+        emap = self.error_map[index:index + 1] if (self.error_map is not None and self.training) else None
+        r = get_rays(self.poses[index:index + 1], self.intrinsics, self.H, self.W, self.num_rays, error_map=emap)
         inds = r["inds"][0]
         out = {"H": self.H, "W": self.W, "rays_o": r["rays_o"], "rays_d": r["rays_d"], "index": [index]}
+        if "inds_coarse" in r:
+            out["inds_coarse"] = r["inds_coarse"]
         img = self.images[index].reshape(-1, 3)
         out["images"] = img[inds.to(img.device)].to(self.device)[None] if self.training else \
             self.images[index].to(self.device)[None]

@@ -51,8 +51,8 @@ def get_rays(poses, intrinsics, H, W, N=-1, error_map=None, inds=None, patch=0):
     """poses [B,4,4] (camera-to-world), intrinsics (fx,fy,cx,cy) -> dict(rays_o, rays_d [B,N,3], inds [B,N]).
 
     Pixel centres at +0.5; dir = ((i-cx)/fx, (j-cy)/fy, 1) normalised, rotated by R; N>0 draws N
-    random pixels (shared across the batch; with ``error_map`` [B, 128*128] they are drawn per batch element
-    in proportion to the map, as upstream).  ``patch=4`` (full images only) enumerates the pixels
+    random pixels (shared across the batch; with ``error_map`` [B, cells*cells] - upstream: 128*128 - they are drawn
+    per batch element in proportion to the map, as upstream, and ``inds_coarse`` [B,N] names the cells).  ``patch=4`` (full images only) enumerates the pixels
     4x4-patch by patch instead of row-major - same rays, an order the renderer's patch-interleaved
     layout turns into compact tiles; scatter results back with ``image.view(-1,3)[inds] = pred``.
     """
@@ -62,9 +62,10 @@ def get_rays(poses, intrinsics, H, W, N=-1, error_map=None, inds=None, patch=0):
     if inds is None and N > 0 and error_map is not None:
         # upstream's importance sampling: draw coarse cells of the [B, 128*128] error map without replacement,
         # then a uniform pixel inside each cell; every batch element gets its own pixels
+        cells = math.isqrt(error_map.shape[-1])                      # upstream's maps are 128 x 128
         inds_coarse = torch.multinomial(error_map.to(device), N, replacement=False)          # [B, N]
-        cx_, cy_ = torch.div(inds_coarse, 128, rounding_mode="floor"), inds_coarse % 128
-        sx, sy = H / 128, W / 128
+        cx_, cy_ = torch.div(inds_coarse, cells, rounding_mode="floor"), inds_coarse % cells
+        sx, sy = H / cells, W / cells
         px = (cx_ * sx + torch.rand(B, N, device=device) * sx).long().clamp(max=H - 1)
         py = (cy_ * sy + torch.rand(B, N, device=device) * sy).long().clamp(max=W - 1)
         per_batch = px * W + py
@@ -874,6 +875,12 @@ class Trainer:
         if self.ema is not None and isinstance(self.optimizer, FusedAdam):
             self.optimizer.attach_ema(self.ema)        # the average advances inside the optimiser's launch (eager and
             #                                            captured steps: inr_adam_ema_step_multi / _dev)
+        # upstream's --error_map: train() adopts the training dataset's map (NeRFDataset(error_map=True)); stage "nerf"
+        # then folds every step's per-ray loss back into the row of the step's image (train_step).  Not checkpointed
+        # (upstream's behaviour); one map per rank.  The captured step was not extended to it: see _adopt_error_map.
+        self.error_map = None
+        self._graph_requested = bool(use_graph)
+        self._error_map_warned = False
         self._graph = None                             # captured.CapturedStep (use_graph)
         self._pipe = None                              # captured.StepPipeline (use_graph and look_ahead)
         self._capacity = HeldCapacity()                # the captured steps' sample-buffer size: outlives load_checkpoint
@@ -947,7 +954,11 @@ class Trainer:
         if self.stage == "nerf":
             pred = outputs["image"]
             loss = outputs["image_mse"] if "image_mse" in outputs else self.criterion(pred, gt).mean()
+            if self.error_map is not None and "inds_coarse" in data:
+                self._update_error_map(data, pred, gt)
             return pred, gt, loss
+        if "inds_coarse" in data:
+            self._adopt_error_map(self.error_map)       # instance stage: the map is left alone (warns once)
         logits = outputs["instance"]
         K = logits.shape[-1]
         if "instance_ce" in outputs:
@@ -958,6 +969,41 @@ class Trainer:
         else:
             loss = torch.nn.functional.cross_entropy(logits.reshape(-1, K), data["masks"].reshape(-1).long(), ignore_index=-1)
         return logits, data["masks"], loss
+
+    def _adopt_error_map(self, error_map):
+        """``self.error_map = train_loader._data.error_map`` (upstream's ``Trainer.train``), plus what this trainer does
+        not do with one: the instance stage leaves the map alone, and ``use_graph=True`` trains on the eager step."""
+        import warnings
+        self.error_map = error_map
+        if self.stage != "nerf":
+            if not self._error_map_warned:
+                self._error_map_warned = True
+                warnings.warn("Trainer: the error map is only updated in stage 'nerf'; stage "
+                              f"{self.stage!r} draws from it and leaves it unchanged", RuntimeWarning, stacklevel=3)
+            return
+        if error_map is not None and self._graph_requested:
+            # the captured step records neither the loader's launch nor the map's update: such a run trains eagerly
+            self._graph_requested = self.use_graph = False
+            self._graph = self._pipe = None
+            warnings.warn("Trainer: use_graph=True is not available with an error map (error_map=True); "
+                          "training on the eager step", RuntimeWarning, stacklevel=3)
+
+    @torch.no_grad()
+    def _update_error_map(self, data, pred, gt):
+        """upstream's update in ``train_step``: ``error = criterion(pred, gt).mean(-1)`` per ray, then an exponential
+        average into the cells the batch was drawn from, ``map[index, inds_coarse] = 0.1 * old + 0.9 * error``.  Default
+        criterion on the GPU: one launch (``inr_error_map_update``); otherwise upstream's tensor expression.  No host
+        read-back either way."""
+        index = data["index"]
+        row = self.error_map[int(index[0] if isinstance(index, (list, tuple)) else index)]
+        inds = data["inds_coarse"].reshape(-1)
+        if self._default_criterion and pred.is_cuda and gt.is_cuda and row.is_cuda and inds.is_cuda:
+            from .. import raymarching
+            raymarching.error_map_update(pred, gt, inds, row, math.isqrt(row.numel()))
+            return
+        error = self.criterion(pred.detach(), gt).mean(-1).reshape(-1).to(row.device)
+        inds = inds.to(row.device)
+        row.scatter_(0, inds, 0.1 * row.gather(0, inds) + 0.9 * error)
 
     @staticmethod
     def _as_image(t, data, channels=None):
@@ -1131,6 +1177,8 @@ class Trainer:
         test and march are then queued on a side stream under this step's backward (``train_one_epoch`` looks one batch
         ahead; same results, ~45 us per step less)."""
         self.model.train()
+        if self._graph_requested and self.error_map is not None and self.stage == "nerf" and "inds_coarse" in data:
+            self._adopt_error_map(self.error_map)       # a map set by hand (not through train()): eager step, one warning
         if self.model.cuda_ray and self.global_step % self.update_extra_interval == 0:
             self.model.update_extra_state()
             if self.use_graph and self.model.mean_count > 0:
@@ -1195,6 +1243,9 @@ class Trainer:
             d = getattr(train_loader, "_data", None)
             if d is not None and hasattr(d, "poses") and hasattr(d, "intrinsics"):
                 self.model.mark_untrained_grid(d.poses, d.intrinsics)
+        d = getattr(train_loader, "_data", None)
+        if getattr(d, "error_map", None) is not None:
+            self._adopt_error_map(d.error_map)          # upstream: self.error_map = train_loader._data.error_map
         for _ in range(self.epoch + 1, self.epoch + max_epochs + 1):
             self.epoch += 1
             self.train_one_epoch(train_loader)

@@ -104,6 +104,52 @@ def sph_from_ray(rays_o, rays_d, radius):
     return torch.where((t >= 0).unsqueeze(-1), coords, torch.full_like(coords, float("nan")))
 
 
+def sample_training_batch_weighted(pose, intrinsics, H, W, image, mask, num_instances, error_map, cells, seed, step, n):
+    """One training batch of ONE image with the pixels drawn from its row of a coarse error map, in one launch
+    (``inr_sample_training_batch_weighted``, include/inr.h: a weighted draw of ``n`` of the ``cells * cells`` cells
+    without replacement - ``torch.multinomial``'s distribution, reproducible from (seed, step) -, a uniform pixel inside
+    each, then rays / colours / labels as the uniform loader).  pose [4,4], image float [H,W,C] (C = 3 or 4),
+    mask int32 [H,W] or None, error_map float [cells*cells].
+    -> dict(inds_coarse, inds int64 [n]; rays_o, rays_d [n,3]; rgb [n,C]; labels int64 [n] or None)."""
+    lib = _lib.load()
+    dev, n = pose.device, int(n)
+    C = int(image.shape[-1])
+    inds = torch.empty(n, dtype=torch.int64, device=dev)
+    coarse = torch.empty(n, dtype=torch.int64, device=dev)
+    rays_o = torch.empty(n, 3, dtype=F32, device=dev)
+    rays_d = torch.empty(n, 3, dtype=F32, device=dev)
+    rgb = torch.empty(n, C, dtype=F32, device=dev)
+    labels = torch.empty(n, dtype=torch.int64, device=dev) if mask is not None else None
+    fx, fy, cx, cy = intrinsics
+    none = n == 0
+    check(lib.inr_sample_training_batch_weighted(
+        ptr(pose, F32, "pose"), float(fx), float(fy), float(cx), float(cy), int(H), int(W), ptr(image, F32, "image"), C,
+        ptr(mask, I32, "mask") if mask is not None else None, int(num_instances or (1 << 30)),
+        ptr(error_map, F32, "error_map"), int(cells), int(seed), int(step), n, ptr(inds, allow_none=none),
+        ptr(coarse, allow_none=none), ptr(rays_o, allow_none=none), ptr(rays_d, allow_none=none),
+        ptr(rgb, allow_none=none), ptr(labels, allow_none=none) if labels is not None else None, stream_ptr()),
+        "sample_training_batch_weighted")
+    return {"inds_coarse": coarse, "inds": inds, "rays_o": rays_o, "rays_d": rays_d, "rgb": rgb, "labels": labels}
+
+
+def error_map_update(pred, target, inds_coarse, error_map, cells):
+    """``error_map[inds_coarse] = 0.1 * error_map[inds_coarse] + 0.9 * mean((pred - target)^2, -1)`` in place, one launch
+    (``inr_error_map_update``; upstream's update of ``Trainer.error_map`` for the default MSE criterion).  pred, target
+    [N,3]; inds_coarse int64 [N] (distinct); error_map float [cells*cells], ONE image's row (a contiguous view)."""
+    lib = _lib.load()
+    pred, target = _f(pred.detach()).view(-1, 3), _f(target.detach()).view(-1, 3)
+    inds_coarse = inds_coarse.reshape(-1)
+    N = pred.shape[0]
+    if target.shape[0] != N or inds_coarse.shape[0] != N:
+        raise RuntimeError(f"error_map_update: {N} predictions, {target.shape[0]} targets, {inds_coarse.shape[0]} indices")
+    if error_map.numel() != int(cells) * int(cells):
+        raise RuntimeError(f"error_map_update: the map row has {error_map.numel()} cells, expected {int(cells) ** 2}")
+    check(lib.inr_error_map_update(ptr(pred, F32, "pred", allow_none=N == 0), ptr(target, F32, "target", allow_none=N == 0),
+                                   ptr(inds_coarse, torch.int64, "inds_coarse", allow_none=N == 0),
+                                   ptr(error_map, F32, "error_map"), N, int(cells), stream_ptr()), "error_map_update")
+    return error_map
+
+
 def morton3D(coords):
     """coords int32 [N,3] (each < 1024) -> int32 [N]."""
     lib = _lib.load()
