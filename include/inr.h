@@ -40,7 +40,9 @@ extern "C" {
  * 10: inr_instance_lattice, inr_instance_volume_stats.
  * 11: the fp16 variants folded into their base entry points as a `numerics` argument (INR_NUMERICS_*).
  * 12: inr_mesh_workspace_bytes, inr_mesh_count, inr_mesh_emit.
- * 13: inr_components_workspace_bytes, inr_components_label, inr_components_filter. */
+ * 13: inr_components_workspace_bytes, inr_components_label, inr_components_filter.
+ * (inr_ssim_workspace_bytes and inr_ssim_forward were ADDED under 13: no prototype changed, nothing was removed; a
+ * library built before them is named by the binding's loader, symbol by symbol.) */
 #define INR_ABI_VERSION 13
 #define INR_MAX_LEVELS 16
 
@@ -1032,6 +1034,47 @@ int inr_finish_rays_mse(const float* image /*[N,3]*/, const float* depth /*[N]*/
                         const float* nears, const float* fars, float bg_r, float bg_g, float bg_b,
                         const float* bg_rays /*[N,3] nullable*/, const float* target /*[N,3]*/, int64_t N,
                         float* image_out, float* depth_out, float* grad /*[4N]*/, float* loss /*[1]*/, inr_stream_t s);
+
+/* ---- Image quality of rendered views: SSIM and the squared error in one launch (csrc/ssim.hip) ----------------------
+ * Upstream's nerf/utils.py evaluates held-out views with PSNRMeter and SSIMMeter [U]; this is the kernel behind
+ * instance_nerf_amd.metrics.image_quality and nerf.utils.SSIMMeter.  The reference project has no counterpart.
+ *
+ * Inputs: pred, truth float32 [B, H, W, C], dense and channels-last (the layout the renderer writes); 1 <= C <= 4;
+ * H, W >= 11 (smaller: INR_EINVAL); B*H*W*C < 2^31; B and the number of tile rows <= 65535.
+ * Window: separable, 11 taps, sigma 1.5: g[i] = exp(-(i-5)^2 / (2 sigma^2)), normalised to sum 1 in binary64, THEN
+ * rounded to binary32 - those eleven binary32 values are the contract (instance_nerf_amd.metrics.gaussian_window).  The
+ * caller computes them and passes them in `window11` (HOST memory, finite values; they travel as kernel arguments).
+ * Valid windows only: the map is [B, H-10, W-10, C]; map pixel (i, j) covers input rows i..i+10 and columns j..j+10
+ * (believed to equal torchmetrics' reflect-pad-then-crop default; not verified).
+ * Per window and channel, with E[.] the windowed sum:  mu_x = E[x], mu_y = E[y], var_x = E[x^2] - mu_x^2, var_y likewise,
+ * cov = E[xy] - mu_x mu_y, and
+ *   SSIM = ((2 mu_x mu_y + C1) (2 cov + C2)) / ((mu_x^2 + mu_y^2 + C1) (var_x + var_y + C2)),  C1 = (0.01 L)^2, C2 = (0.03 L)^2.
+ * L = data_range_dev[0], ONE float on the device (so neither a constant nor a range inferred by device reductions is
+ * read back by the caller).
+ * Arithmetic of the kernel (tests/ssim_reference.py restates it in binary32): a workgroup owns a tile of
+ * INR_SSIM_TILE_W x INR_SSIM_TILE_H map pixels; per channel its pivot p is the truth pixel at the tile's first window
+ * centre (row 16 ty + 5, column 64 tx + 5; 0 when that pixel is not finite); moments are taken of x - p and y - p
+ * (variances and the covariance do not move under the shift - up to the 2-D window's |sum - 1| = 2.8e-9 - and lose far less to
+ * cancellation), mu = shifted mean + p.  Products first (binary32), then the horizontal pass, then the vertical pass,
+ * each acc = g[0] v0, acc = acc + g[k] vk for k = 1..10 with separate multiplies and adds; the formula as written above
+ * with 2 (mu_x mu_y), an IEEE division.  Identical images give exactly 1.0f.
+ * out_ssim [B] = mean of the map over valid pixels and channels (map entries are added in binary64, divided, rounded
+ * to binary32).  out_sse [B] (nullable) = sum over ALL H*W*C elements of (pred - truth)^2: difference and square in
+ * binary32, added in binary64, every input pixel counted exactly once (a tile owns its map rectangle shifted by (5, 5);
+ * tiles on an image edge also own the 5-pixel border on that side).  out_map (nullable) receives the map.
+ * Non-finite inputs are not masked: a NaN or +-inf under a window makes that map entry NaN and the image's mean with
+ * it; a NaN pixel makes that image's sse NaN; other images of the batch are untouched.
+ * Determinism: no float atomics.  Each workgroup writes its two binary64 partial sums into its own slot of `workspace`
+ * (inr_ssim_workspace_bytes(B, H, W, C) bytes, 8-byte aligned, caller-owned; INR_EINVAL as a negative return for bad
+ * sizes); a second tiny launch inside the same call adds the slots in a fixed order.  Two calls return the same bits. */
+#define INR_SSIM_TAPS 11
+#define INR_SSIM_TILE_W 64
+#define INR_SSIM_TILE_H 16
+int64_t inr_ssim_workspace_bytes(int64_t B, int64_t H, int64_t W, int32_t C);
+int inr_ssim_forward(const float* pred, const float* truth, int64_t B, int64_t H, int64_t W, int32_t C,
+                     const float* window11 /*host, [11]*/, const float* data_range_dev /*[1]*/, float* out_ssim /*[B]*/,
+                     float* out_sse /*[B] nullable*/, float* out_map /*[B,H-10,W-10,C] nullable*/, void* workspace,
+                     int64_t workspace_bytes, inr_stream_t s);
 
 #ifdef __cplusplus
 }

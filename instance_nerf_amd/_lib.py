@@ -19,6 +19,7 @@ GRID_FX_STATE_FLOATS = 4192      # include/inr.h INR_GRID_FX_STATE_FLOATS
 ROI_MAX_LEVELS = 8               # include/inr.h INR_ROI_MAX_LEVELS
 NUMERICS_TABLE_F16, NUMERICS_MLP_F16 = 1, 2      # include/inr.h INR_NUMERICS_*
 RAY_TABLE_FLOATS = 24            # include/inr.h INR_RAY_TABLE_FLOATS
+SSIM_TAPS, SSIM_TILE_W, SSIM_TILE_H = 11, 64, 16    # include/inr.h INR_SSIM_TAPS, INR_SSIM_TILE_W, INR_SSIM_TILE_H
 
 
 class GridDesc(Structure):
@@ -174,6 +175,8 @@ _SIGS = {
     "inr_background_forward": (c_int32, [P, P, c_int64, c_float, P, POINTER(GridDesc), P, P, P, P, P, P, P]),
     "inr_background_workspace_bytes": (c_int64, [c_int64]),
     "inr_background_backward": (c_int32, [P, P, P, c_int64, c_float, P, POINTER(GridDesc), P, P, P, P, P, P, P]),
+    "inr_ssim_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int32]),
+    "inr_ssim_forward": (c_int32, [P, P, c_int64, c_int64, c_int64, c_int32, P, P, P, P, P, P, c_int64, P]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -201,7 +204,10 @@ def load():
         raise RuntimeError(f"{LIB_PATH} ABI version {found} != {ABI_VERSION} (include/inr.h "
                            "INR_ABI_VERSION): rebuild with `python -m instance_nerf_amd.build --force`")
     for name, (res, args) in _SIGS.items():
-        fn = getattr(lib, name)         # AttributeError if the symbol is not exported
+        fn = getattr(lib, name, None)
+        if fn is None:                  # exports added without a version bump (inr_ssim_*): a library built before them
+            raise RuntimeError(f"{LIB_PATH} does not export {name} (include/inr.h): rebuild with "
+                               "`python -m instance_nerf_amd.build --force`")
         fn.restype = res
         fn.argtypes = args
     _lib = lib

@@ -146,6 +146,58 @@ class PSNRMeter:
         return f"PSNR = {self.measure():.6f}"
 
 
+class SSIMMeter:
+    """Mean structural similarity of the evaluated views (upstream's name [U]; semantics: instance_nerf_amd.metrics).
+    ``update`` takes [B, H, W, C] or [H, W, C] images and accumulates on the device - a running sum of the per-image SSIM
+    and a count - so it never reads back and the pipelined view loop keeps running; ``measure`` reads back once.  The
+    fused kernel returns the squared error of the same launch: ``with_psnr`` also accumulates PSNRMeter's figure (one
+    value per update, from the mse over the whole update).  ``device``: where the sums live (default: the first update's).
+    A 3-D input is ambiguous: it is read as ONE image [H, W, C] when its first extent is at least 11 (one window) and
+    refused as a flat [B, N, C] batch otherwise - so a flat batch of 11 or more views, e.g. [16, 4096, 3], is NOT detected
+    and would be scored as a 16 x 4096 image.  Loaders hand over [B, H, W, C] (``Trainer._as_image`` restores it from the
+    batch's 'H' and 'W'); pass 4-D tensors whenever the batch can hold 11 views or more."""
+
+    def __init__(self, data_range=1.0, with_psnr=False, device=None):
+        self.data_range, self.with_psnr, self.device = data_range, with_psnr, device
+        self.clear()
+
+    def clear(self):
+        self.sums = None           # [ssim sum, psnr sum] float64 on the device, made by the first update
+        self.N, self.updates = 0, 0
+
+    def update(self, preds, truths):
+        from ..metrics import image_quality
+        # a 3-D input is an image only when its first extent can be a height (>= 11, one window): [B, N, C] is a flat batch
+        if preds.dim() not in (3, 4) or (preds.dim() == 3 and preds.shape[0] < 11):
+            raise ValueError(f"SSIMMeter needs images [B, H, W, C] or [H, W, C], got {tuple(preds.shape)}: a flat [B, N, C] "
+                             "batch has no rows and columns - the loader's batch must carry 'H' and 'W' so that the "
+                             "evaluation step can restore them")
+        q = image_quality(preds, truths, data_range=self.data_range)
+        dev = torch.device(self.device) if self.device is not None else q["ssim"].device
+        if self.sums is None:
+            self.sums = torch.zeros(2, dtype=torch.float64, device=dev)
+        self.sums[0] += q["ssim"].double().sum().to(dev)
+        if self.with_psnr:
+            mse = q["mse"].double().mean()         # images of one update have one size: the mean of the per-image mse is the update's mse
+            self.sums[1] += (-10.0 * torch.log10(torch.clamp(mse, min=1e-12))).to(dev)
+        self.N += q["ssim"].shape[0]
+        self.updates += 1
+
+    def measure_both(self):
+        """-> (mean SSIM, mean PSNR or None); the one read-back."""
+        if self.sums is None:
+            return 0.0, (0.0 if self.with_psnr else None)
+        s = self.sums.tolist()
+        return s[0] / max(self.N, 1), (s[1] / max(self.updates, 1) if self.with_psnr else None)
+
+    def measure(self):
+        return self.measure_both()[0]
+
+    def report(self):
+        ssim, psnr = self.measure_both()
+        return f"SSIM = {ssim:.6f}" + (f", PSNR = {psnr:.6f}" if self.with_psnr else "")
+
+
 class MIoUMeter:
     """Mean IoU over the instance ids present in the ground truth (ignore label -1).  Until round 4 the mean ran over
     every id with a non-empty union, i.e. also over ids that only the PREDICTION contains: a handful of stray pixels of
