@@ -42,7 +42,8 @@ extern "C" {
  * 12: inr_mesh_workspace_bytes, inr_mesh_count, inr_mesh_emit.
  * 13: inr_components_workspace_bytes, inr_components_label, inr_components_filter.
  * (inr_ssim_workspace_bytes and inr_ssim_forward were ADDED under 13: no prototype changed, nothing was removed; a
- * library built before them is named by the binding's loader, symbol by symbol.) */
+ * library built before them is named by the binding's loader, symbol by symbol.  inr_confusion_ids and
+ * inr_confusion_logits likewise.) */
 #define INR_ABI_VERSION 13
 #define INR_MAX_LEVELS 16
 
@@ -1075,6 +1076,41 @@ int inr_ssim_forward(const float* pred, const float* truth, int64_t B, int64_t H
                      const float* window11 /*host, [11]*/, const float* data_range_dev /*[1]*/, float* out_ssim /*[B]*/,
                      float* out_sse /*[B] nullable*/, float* out_map /*[B,H-10,W-10,C] nullable*/, void* workspace,
                      int64_t workspace_bytes, inr_stream_t s);
+
+/* ---- Segmentation confusion matrix of rendered instance maps (csrc/confusion.hip) -----------------------------------
+ * The joint (truth id, predicted id) histogram of B images of N pixels each: the one object from which mIoU, pixel
+ * accuracy, per-pair IoU and panoptic quality follow exactly (instance_nerf_amd.metrics.segmentation_confusion /
+ * segmentation_scores, nerf.utils.SegmentationMeter).  The reference project has no counterpart.
+ *
+ * Matrix: counts int64 [B, K, K+1], 1 <= K <= INR_CONFUSION_MAX_K (the project's limit on instance channels).
+ * counts[b, t, p] = number of pixels of image b with truth id t and predicted id p, both in [0, K).  Column K collects
+ * the pixels whose truth is valid but whose prediction lies outside [0, K): row sums stay equal to the truth areas, and
+ * such a pixel counts towards the truth and the union of t and towards no prediction (what nerf.utils.MIoUMeter does
+ * with it).
+ * Ignored pixels: ignored int64 [B].  A pixel whose truth lies outside [0, K) - the ignore label -1, any other negative
+ * value, any value >= K - is counted there and nowhere else, whatever its prediction.
+ * Accumulation: a call ADDS into counts and ignored; the caller zeroes them.  A meter accumulates a whole scene in place,
+ * one call per update, and nothing is read back.
+ * Arithmetic: integer atomics only (32-bit in LDS per workgroup, one 64-bit global add per non-zero counter at the end):
+ * two calls give the same bits.  A workgroup of INR_CONFUSION_BLOCK threads owns a run of INR_CONFUSION_PIXELS_PER_WG
+ * consecutive pixels of one image.
+ * Two entry points share the histogram code:
+ *   inr_confusion_ids     pred int32 [B, N], truth int32 [B, N].
+ *   inr_confusion_logits  logits float32 [B, N, ld] with ld >= K the row stride in floats, truth int32 [B, N].  The
+ *                         prediction is the arg-max over channels 0 .. K-1 only; channels K .. ld-1 are never read.
+ * Arg-max rule: NaN compares greater than every number; among equal maxima - several NaN, or equal numbers, so -0.0 and
+ * +0.0 tie - the lowest index wins.  This is torch.argmax on CPU tensors.
+ * Bad arguments are INR_EINVAL with a message, before any launch: K outside [1, 64], ld < K, negative B or N,
+ * B*N*ld >= 2^63 (element indices are 64-bit) or more than 2^31 - 1 workgroups (B * ceil(N / INR_CONFUSION_PIXELS_PER_WG)),
+ * null pointers, counts or ignored not 8-byte aligned.  B == 0 or N == 0 is a valid no-op returning 0 (sizes, K and ld are
+ * still checked; no pointer is looked at).                                                                            */
+#define INR_CONFUSION_MAX_K 64
+#define INR_CONFUSION_BLOCK 256
+#define INR_CONFUSION_PIXELS_PER_WG 1024
+int inr_confusion_ids(const int32_t* pred /*[B,N]*/, const int32_t* truth /*[B,N]*/, int64_t B, int64_t N, int32_t K,
+                      int64_t* counts /*[B,K,K+1]*/, int64_t* ignored /*[B]*/, inr_stream_t s);
+int inr_confusion_logits(const float* logits /*[B,N,ld]*/, const int32_t* truth /*[B,N]*/, int64_t B, int64_t N, int32_t K,
+                         int64_t ld, int64_t* counts /*[B,K,K+1]*/, int64_t* ignored /*[B]*/, inr_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -20,6 +20,8 @@ ROI_MAX_LEVELS = 8               # include/inr.h INR_ROI_MAX_LEVELS
 NUMERICS_TABLE_F16, NUMERICS_MLP_F16 = 1, 2      # include/inr.h INR_NUMERICS_*
 RAY_TABLE_FLOATS = 24            # include/inr.h INR_RAY_TABLE_FLOATS
 SSIM_TAPS, SSIM_TILE_W, SSIM_TILE_H = 11, 64, 16    # include/inr.h INR_SSIM_TAPS, INR_SSIM_TILE_W, INR_SSIM_TILE_H
+# include/inr.h INR_CONFUSION_MAX_K, INR_CONFUSION_BLOCK, INR_CONFUSION_PIXELS_PER_WG
+CONFUSION_MAX_K, CONFUSION_BLOCK, CONFUSION_PIXELS_PER_WG = 64, 256, 1024
 
 
 class GridDesc(Structure):
@@ -177,6 +179,8 @@ _SIGS = {
     "inr_background_backward": (c_int32, [P, P, P, c_int64, c_float, P, POINTER(GridDesc), P, P, P, P, P, P, P]),
     "inr_ssim_workspace_bytes": (c_int64, [c_int64, c_int64, c_int64, c_int32]),
     "inr_ssim_forward": (c_int32, [P, P, c_int64, c_int64, c_int64, c_int32, P, P, P, P, P, P, c_int64, P]),
+    "inr_confusion_ids": (c_int32, [P, P, c_int64, c_int64, c_int32, P, P, P]),
+    "inr_confusion_logits": (c_int32, [P, P, c_int64, c_int64, c_int32, c_int64, P, P, P]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -205,7 +209,7 @@ def load():
                            "INR_ABI_VERSION): rebuild with `python -m instance_nerf_amd.build --force`")
     for name, (res, args) in _SIGS.items():
         fn = getattr(lib, name, None)
-        if fn is None:                  # exports added without a version bump (inr_ssim_*): a library built before them
+        if fn is None:                  # exports added without a version bump (inr_ssim_*, inr_confusion_*): a library built before them
             raise RuntimeError(f"{LIB_PATH} does not export {name} (include/inr.h): rebuild with "
                                "`python -m instance_nerf_amd.build --force`")
         fn.restype = res

@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libinr_hip.so")
 SOURCES = ["raymarch.hip", "encoders.hip", "field_fused.hip", "roialign.hip", "mesh.hip", "components.hip", "match.hip",
-           "overlap.hip", "detect.hip", "background.hip", "ssim.hip"]
+           "overlap.hip", "detect.hip", "background.hip", "ssim.hip", "confusion.hip"]
 HEADERS = ["common.h", "grid_common.h", "sample_pos.h", os.path.join("..", "..", "include", "inr.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function"]
@@ -26,6 +26,7 @@ KERNEL_FILES = {
     "scatter": ["encoders.hip", "common.h", "grid_common.h"],         # k_grid_bwd, k_adam_*
     "background": ["background.hip", "common.h", "grid_common.h"],    # k_background_fwd, k_background_bwd, k_sph_from_ray
     "ssim": ["ssim.hip", "common.h"],                                 # k_ssim_tiles, k_ssim_finish
+    "confusion": ["confusion.hip", "common.h"],                       # k_confusion_ids, k_confusion_logits
 }
 
 

@@ -240,6 +240,77 @@ class MIoUMeter:
         return f"mIoU = {b['miou_gt_ids']:.6f} (over ground-truth ids; {b['miou_all_ids']:.6f} counting ids only predicted)"
 
 
+class SegmentationMeter:
+    """Scene-level segmentation scores from ONE confusion matrix accumulated over every evaluated view (semantics:
+    include/inr.h "Segmentation confusion matrix of rendered instance maps", instance_nerf_amd.metrics).  ``update`` takes
+    predicted ids (integers, truth's shape) or logits (floating point, one more trailing dimension of at least
+    ``num_classes`` channels) and integer truths, adds the update's pixels into ``counts`` [K, K+1] / ``ignored`` [1] on
+    the device of the first update (or ``device``) and reads nothing back, so the pipelined view loop keeps running.
+    ``measure()`` is ``miou_gt_ids`` - MIoUMeter's figure on the same pixels, bit for bit; higher is better, so the meter
+    can be ``metrics[0]`` of a Trainer.  ``measure_all()`` - the one read-back - is the dict of
+    ``metrics.segmentation_scores(counts, stuff_ids, match)`` plus ``counts`` and ``ignored`` (CPU tensors).
+    ``reduce(group)`` all-reduces the integers, so a sharded evaluation scores the exact scene matrix, not an average of
+    per-rank ratios."""
+
+    def __init__(self, num_classes, stuff_ids=(0,), match="id", device=None):
+        if match not in ("id", "any"):
+            raise ValueError(f"match must be 'id' or 'any', got {match!r}")
+        self.K, self.stuff_ids, self.match, self.device = int(num_classes), tuple(stuff_ids), match, device
+        self.clear()
+
+    def clear(self):
+        self._out = None            # (counts [1, K, K+1], ignored [1]) int64, made by the first update
+
+    @property
+    def counts(self):
+        return None if self._out is None else self._out[0][0]
+
+    @property
+    def ignored(self):
+        return None if self._out is None else self._out[1]
+
+    def _buffers(self, device):
+        if self._out is None:
+            self._out = (torch.zeros((1, self.K, self.K + 1), dtype=torch.int64, device=device),
+                         torch.zeros((1,), dtype=torch.int64, device=device))
+        return self._out
+
+    def update(self, preds, truths):
+        from ..metrics import segmentation_confusion
+        dev = torch.device(self.device) if self.device is not None else (
+            truths.device if self._out is None else self._out[0].device)
+        preds, truths = preds.detach().to(dev), truths.detach().to(dev)
+        # the whole update is one image of the matrix: views only ever add up
+        flat = truths.reshape(1, -1)
+        preds = preds.reshape(1, flat.shape[1], preds.shape[-1]) if preds.dtype.is_floating_point else preds.reshape(1, -1)
+        segmentation_confusion(preds, flat, self.K, out=self._buffers(dev))
+
+    def reduce(self, group=None):
+        """Sums counts and ignored over the ranks of ``group`` (default: the world), in place: every rank then holds the
+        matrix of all ranks' views.  A rank that saw no view contributes zeros (on ``device``, or the CPU)."""
+        dev = torch.device(self.device) if self.device is not None else torch.device("cpu")
+        for t in self._buffers(dev):
+            dist.all_reduce(t, group=group)
+
+    def measure_all(self):
+        from ..metrics import segmentation_scores
+        if self._out is None:          # nothing seen: all zeros, and the first update still chooses the device
+            counts, ignored = torch.zeros((1, self.K, self.K + 1), dtype=torch.int64), torch.zeros((1,), dtype=torch.int64)
+        else:
+            counts, ignored = [t.cpu() for t in self._out]
+        out = segmentation_scores(counts, stuff_ids=self.stuff_ids, match=self.match)
+        out["counts"], out["ignored"] = counts[0], ignored
+        return out
+
+    def measure(self):
+        return self.measure_all()["miou_gt_ids"]
+
+    def report(self):
+        s = self.measure_all()
+        return (f"mIoU = {s['miou_gt_ids']:.6f} (over ground-truth ids; {s['miou_all_ids']:.6f} counting ids only predicted), "
+                f"pixel acc = {s['pixel_acc']:.6f}, PQ = {s['pq']:.6f} (SQ {s['sq']:.6f}, RQ {s['rq']:.6f}; match={self.match!r})")
+
+
 class FusedAdam(torch.optim.Optimizer):
     """Adam(betas, eps) with one fused HIP sweep for all tensors of a step (reads p,g,m,v; writes p,m,v once).
 
@@ -1397,6 +1468,44 @@ class Trainer:
         for m in meters:
             self.log(m.report())
         return result
+
+    @torch.no_grad()
+    def evaluate_segmentation(self, loader, stuff_ids=(0,), match="id", name=None):
+        """Scores the instance field's rendered id maps against the batches' ``masks`` over ALL views of ``loader`` at
+        once - the 2-D counterpart of ``evaluate_instance_masks``: mIoU (both definitions), pixel accuracy and scene-level
+        panoptic quality from one confusion matrix (``SegmentationMeter``; ``stuff_ids`` and ``match`` as in
+        ``metrics.segmentation_scores``).  Evaluates what ``evaluate_one_epoch`` evaluates - eval mode, the averaged
+        parameters when an EMA is kept, the pipelined view loop - and restores the state afterwards.  The rendered logits
+        go to the meter as they are (the arg-max happens inside the histogram kernel; no id map is made, nothing is read
+        back per view); with ``world_size > 1`` the integers are all-reduced, so every rank returns the matrix of all
+        ranks' views.  Touches neither ``stats`` nor the caller's metrics.  Logs the meter's report.
+        -> ``SegmentationMeter.measure_all()``."""
+        if self.stage != "instance" or int(getattr(self.model, "num_instances", 0) or 0) < 1:
+            raise ValueError("evaluate_segmentation needs the instance stage: this trainer's model has no instance head "
+                             f"(stage {self.stage!r})")
+        meter = SegmentationMeter(self.model.num_instances, stuff_ids=stuff_ids, match=match, device=self.device)
+        was_training = self.model.training
+        self.model.eval()
+        self._sync_shards()
+        if self.ema is not None:
+            self.ema.store()
+            self.ema.copy_to()
+        try:
+            for i, (data, outputs) in enumerate(self.render_sequence(loader)):
+                if "masks" not in data:
+                    raise ValueError(f"evaluate_segmentation: batch {i} of the loader has no 'masks' (ground-truth ids)")
+                if "instance" not in outputs:
+                    raise ValueError("evaluate_segmentation: the renderer returned no 'instance' logits")
+                logits = outputs["instance"]
+                meter.update(logits.float().contiguous(), data["masks"].reshape(logits.shape[0], -1))
+        finally:
+            if self.ema is not None:
+                self.ema.restore()
+            self.model.train(was_training)
+        if self.world_size > 1:
+            meter.reduce()
+        self.log(f"==> segmentation{' ' + name if name else ''}: " + meter.report())
+        return meter.measure_all()
 
     @torch.no_grad()
     def test(self, loader, save_path=None, name=None, write_video=False):
