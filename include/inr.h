@@ -43,7 +43,7 @@ extern "C" {
  * 13: inr_components_workspace_bytes, inr_components_label, inr_components_filter.
  * (inr_ssim_workspace_bytes and inr_ssim_forward were ADDED under 13: no prototype changed, nothing was removed; a
  * library built before them is named by the binding's loader, symbol by symbol.  inr_confusion_ids and
- * inr_confusion_logits likewise.) */
+ * inr_confusion_logits likewise, and inr_box_match_gt_max and inr_box_match_assign.) */
 #define INR_ABI_VERSION 13
 #define INR_MAX_LEVELS 16
 
@@ -1111,6 +1111,57 @@ int inr_confusion_ids(const int32_t* pred /*[B,N]*/, const int32_t* truth /*[B,N
                       int64_t* counts /*[B,K,K+1]*/, int64_t* ignored /*[B]*/, inr_stream_t s);
 int inr_confusion_logits(const float* logits /*[B,N,ld]*/, const int32_t* truth /*[B,N]*/, int64_t B, int64_t N, int32_t K,
                          int64_t ld, int64_t* counts /*[B,K,K+1]*/, int64_t* ignored /*[B]*/, inr_stream_t s);
+
+/* ---- Detector training targets (csrc/assign.hip, csrc/box_iou.h) ----------------------------------------------------
+ * What every RPN step and every RoI-head step of the reference starts with: a ground-truth box for each anchor or
+ * proposal (model/rpn.py:240-290, nerf_rcnn.py:464-498: batched_box_iou, Matcher, model/utils.py:100-214,375-462) and
+ * the regression targets of the box coder (coder/AABB_coder.py:7-56), without the [G, A] quality matrix.  Additive: no
+ * version bump.
+ *
+ * Inputs: gt fp32 [G, 6] and boxes fp32 [A, 6], rows (x1, y1, z1, x2, y2, z2); valid uint8 [A], nullable: the
+ * reference's padding mask (non-zero = a real box).
+ * Quality: q[g, a] = the reference's AABB IoU of GT box g and box a, all in fp32, every operation rounded on its own (no
+ * fused multiply-add), IEEE division: volume = ((x2 - x1) * (y2 - y1)) * (z2 - z1); extents e = min(hi) - max(lo)
+ * clamped at 0; inter = (e0 * e1) * e2; q = inter / ((volume_gt + volume_box) - inter).  min, max and the clamp keep a
+ * NaN operand (torch's rule); 0 / 0 is a NaN.  A box with valid == 0 has q[:, a] = -1.0f.
+ * Row maxima: gt_max[g] = the maximum of q[g, :], a NaN above every number, kept as an order-preserving uint32 key:
+ * NaN -> 0xFFFFFFFF; sign bit set -> ~bits; otherwise bits | 0x80000000 (so -1 sorts below +0).
+ *
+ * inr_box_match_gt_max: gt_max_keys uint32 [G] = those keys.  The call zeroes the keys itself (key 0 is below every
+ *   value), then one launch: a workgroup of INR_BOX_MATCH_BLOCK lanes owns INR_BOX_MATCH_BOXES_PER_WG consecutive boxes,
+ *   keeps the maxima with integer max in LDS and issues at most one global integer max per (workgroup, GT).  Integer
+ *   arithmetic only: two calls give the same bits.
+ * inr_box_match_assign: one lane per box recomputes its G qualities with the same device function and applies the
+ *   Matcher:
+ *     best, arg = the maximum of q[:, a] and its index: the lowest index among equals, a NaN counts as the maximum and
+ *       the first NaN wins (torch.max over dim 0 on CPU tensors);
+ *     matched[a] = arg;  -1 if best < low;  -2 if low <= best < high (fp32 comparisons; a NaN best keeps arg);
+ *     allow_low_quality != 0: if q[g, a] == gt_max[g] for ANY g (float ==, never true for a NaN), matched[a] = arg again.
+ *       This keeps the reference's quirk: a GT whose row maximum is 0 restores every box with IoU 0 against it, and a
+ *       row maximum of -1 (every box masked) restores the masked boxes.
+ *   Outputs: matched int32 [A]; and, each nullable,
+ *     labels int32 [A]: with gt_labels (int32 [G]) gt_labels[matched] for matched >= 0, without it 1; 0 for -1; -1 for
+ *       -2; and -1 wherever valid == 0, applied last (rpn.py:283-285);
+ *     best_iou fp32 [A] = best;
+ *     matched_boxes fp32 [A, 6] = gt[max(matched, 0)];
+ *     targets fp32 [A, 6] = encode_boxes_3d(matched_boxes, boxes): per axis w = x2 - x1, ctr = x1 + 0.5f * w for both
+ *       boxes, (ctr_gt - ctr_box) / w_box in columns 0..2 and logf(w_gt / w_box) in columns 3..5, one fp32 operation at
+ *       a time in that order.
+ *   One launch; nothing is read back.
+ * Limits, checked before any launch (INR_EINVAL with a message): 1 <= G <= INR_BOX_MATCH_MAX_GT (32 B of LDS per GT:
+ * 32 KB), A >= 0, 6 * A < 2^31, low <= high (neither a NaN), gt, boxes, gt_max_keys and matched not null, every array
+ * but valid 4-byte aligned.  A == 0 is a valid no-op returning 0 (G and the thresholds are still checked; no pointer is
+ * looked at, the keys are left alone).                                                                             */
+#define INR_BOX_MATCH_MAX_GT 1024
+#define INR_BOX_MATCH_BLOCK 256
+#define INR_BOX_MATCH_BOXES_PER_WG 1024
+int inr_box_match_gt_max(const float* gt /*[G,6]*/, int32_t G, const float* boxes /*[A,6]*/,
+                         const uint8_t* valid /*[A] nullable*/, int64_t A, uint32_t* gt_max_keys /*[G]*/, inr_stream_t s);
+int inr_box_match_assign(const float* gt /*[G,6]*/, const int32_t* gt_labels /*[G] nullable*/, int32_t G,
+                         const float* boxes /*[A,6]*/, const uint8_t* valid /*[A] nullable*/, int64_t A,
+                         const uint32_t* gt_max_keys /*[G]*/, float high, float low, int32_t allow_low_quality,
+                         int32_t* matched /*[A]*/, int32_t* labels /*[A] nullable*/, float* best_iou /*[A] nullable*/,
+                         float* matched_boxes /*[A,6] nullable*/, float* targets /*[A,6] nullable*/, inr_stream_t s);
 
 #ifdef __cplusplus
 }

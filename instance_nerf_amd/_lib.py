@@ -22,6 +22,8 @@ RAY_TABLE_FLOATS = 24            # include/inr.h INR_RAY_TABLE_FLOATS
 SSIM_TAPS, SSIM_TILE_W, SSIM_TILE_H = 11, 64, 16    # include/inr.h INR_SSIM_TAPS, INR_SSIM_TILE_W, INR_SSIM_TILE_H
 # include/inr.h INR_CONFUSION_MAX_K, INR_CONFUSION_BLOCK, INR_CONFUSION_PIXELS_PER_WG
 CONFUSION_MAX_K, CONFUSION_BLOCK, CONFUSION_PIXELS_PER_WG = 64, 256, 1024
+# include/inr.h INR_BOX_MATCH_MAX_GT, INR_BOX_MATCH_BLOCK, INR_BOX_MATCH_BOXES_PER_WG
+BOX_MATCH_MAX_GT, BOX_MATCH_BLOCK, BOX_MATCH_BOXES_PER_WG = 1024, 256, 1024
 
 
 class GridDesc(Structure):
@@ -181,6 +183,8 @@ _SIGS = {
     "inr_ssim_forward": (c_int32, [P, P, c_int64, c_int64, c_int64, c_int32, P, P, P, P, P, P, c_int64, P]),
     "inr_confusion_ids": (c_int32, [P, P, c_int64, c_int64, c_int32, P, P, P]),
     "inr_confusion_logits": (c_int32, [P, P, c_int64, c_int64, c_int32, c_int64, P, P, P]),
+    "inr_box_match_gt_max": (c_int32, [P, c_int32, P, P, c_int64, P, P]),
+    "inr_box_match_assign": (c_int32, [P, P, c_int32, P, P, c_int64, P, c_float, c_float, c_int32, P, P, P, P, P, P]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -209,7 +213,7 @@ def load():
                            "INR_ABI_VERSION): rebuild with `python -m instance_nerf_amd.build --force`")
     for name, (res, args) in _SIGS.items():
         fn = getattr(lib, name, None)
-        if fn is None:                  # exports added without a version bump (inr_ssim_*, inr_confusion_*): a library built before them
+        if fn is None:                  # exports added without a version bump (inr_ssim_*, inr_confusion_*, inr_box_match_*): a library built before them
             raise RuntimeError(f"{LIB_PATH} does not export {name} (include/inr.h): rebuild with "
                                "`python -m instance_nerf_amd.build --force`")
         fn.restype = res
