@@ -1,7 +1,9 @@
 """Plain numpy (float32) restatement of the iso-surface mesh extraction documented in include/inr.h ("iso-surface meshes of
 a lattice field"): marching tetrahedra over the Kuhn split of every lattice cell.  Written from that comment, not from
 the kernels: vertices are welded through a dictionary keyed by (owner point, direction), triangles come from a loop over
-cells.  It is the yardstick of tests/test_mesh_cpu.py and tests/test_mesh_extract.py, so it stays slow and obvious."""
+cells.  It is the yardstick of tests/test_mesh_cpu.py and tests/test_mesh_extract.py, so it stays slow and obvious; only
+the search for crossed edges and for cells with a surface runs on whole arrays (a lattice of half a million points takes
+seconds, not minutes)."""
 import numpy as np
 
 f32 = np.float32
@@ -66,26 +68,18 @@ def marching_tetrahedra(field, iso, clamp, axes, labels=None, select=-1, rgb=Non
         want_face_labels = labels is not None
 
     # ---- vertices: every crossed edge p -> p + d, ordered by owner point (w, l, h; h fastest), then direction code 1..7
+    # (the crossing test of every (point, direction) is taken on whole arrays; argwhere walks them in exactly that order)
     vertex_id = {}
     owners, ts = [], []
     if min(E) >= 2:
-        for ew in range(E[0]):
-            for el in range(E[1]):
-                row_in = inside[ew, el]
-                # a quick way past rows that cannot hold an owner: every point of the 2 x 2 x H neighbourhood agrees
-                blk = inside[ew:ew + 2, el:el + 2]
-                if blk.all() or not blk.any():
-                    continue
-                for eh in range(E[2]):
-                    for c in range(1, 8):
-                        dw, dl, dh = corner(c)
-                        qw, ql, qh = ew + dw, el + dl, eh + dh
-                        if qw >= E[0] or ql >= E[1] or qh >= E[2]:
-                            continue
-                        if row_in[eh] == inside[qw, ql, qh]:
-                            continue
-                        vertex_id[(ew, el, eh, c)] = len(owners)
-                        owners.append((ew, el, eh, c))
+        crossed = np.zeros(E + (7,), bool)
+        for c in range(1, 8):
+            dw, dl, dh = corner(c)
+            p = inside[:E[0] - dw, :E[1] - dl, :E[2] - dh]
+            crossed[:E[0] - dw, :E[1] - dl, :E[2] - dh, c - 1] = p != inside[dw:, dl:, dh:]
+        for ew, el, eh, k in np.argwhere(crossed).tolist():
+            vertex_id[(ew, el, eh, k + 1)] = len(owners)
+            owners.append((ew, el, eh, k + 1))
     V = len(owners)
     vertices = np.zeros((V, 3), f32)
     colors = np.zeros((V, 3), f32) if rgb is not None else None
@@ -114,39 +108,36 @@ def marching_tetrahedra(field, iso, clamp, axes, labels=None, select=-1, rgb=Non
 
     # ---- triangles: by cell (named by its corner 0) in the same order, then tetrahedron 0..5, then the table's order
     faces, flabels = [], []
-    for ew in range(E[0] - 1):
-        for el in range(E[1] - 1):
-            blk = inside[ew:ew + 2, el:el + 2]
-            if blk.all() or not blk.any():
+    inside_count = np.zeros(tuple(max(n - 1, 0) for n in E), np.int64)
+    if min(E) >= 2:
+        for c in range(8):
+            dw, dl, dh = corner(c)
+            inside_count += inside[dw:E[0] - 1 + dw, dl:E[1] - 1 + dl, dh:E[2] - 1 + dh]
+    for ew, el, eh in np.argwhere((inside_count > 0) & (inside_count < 8)).tolist():       # the cells a surface passes through
+        for t, tet in enumerate(TETS):
+            pts = [(ew + corner(c)[0], el + corner(c)[1], eh + corner(c)[2]) for c in tet]
+            m = sum(1 << i for i in range(4) if inside[pts[i]])
+            tris = CASES[m]
+            if not tris:
                 continue
-            for eh in range(E[2] - 1):
-                cube = inside[ew:ew + 2, el:el + 2, eh:eh + 2]
-                if cube.all() or not cube.any():
-                    continue
-                for t, tet in enumerate(TETS):
-                    pts = [(ew + corner(c)[0], el + corner(c)[1], eh + corner(c)[2]) for c in tet]
-                    m = sum(1 << i for i in range(4) if inside[pts[i]])
-                    tris = CASES[m]
-                    if not tris:
-                        continue
-                    label = 255
-                    if want_face_labels:
-                        best = None
-                        for i in range(4):
-                            if inside[pts[i]] and (best is None or g[pts[i]] > g[pts[best]]):
-                                best = i
-                        bw, bl, bh = pts[best]
-                        label = int(labels[bw - pad, bl - pad, bh - pad])
-                    for tri in tris:
-                        ids = []
-                        for e in tri:
-                            i, j = EDGES[e]
-                            code = tet[j] - tet[i]                 # the corners of a tetrahedron are nested: j adds axes to i
-                            ids.append(vertex_id[pts[i] + (code,)])
-                        if MIRRORED[t]:
-                            ids = [ids[0], ids[2], ids[1]]
-                        faces.append(ids)
-                        flabels.append(label)
+            label = 255
+            if want_face_labels:
+                best = None
+                for i in range(4):
+                    if inside[pts[i]] and (best is None or g[pts[i]] > g[pts[best]]):
+                        best = i
+                bw, bl, bh = pts[best]
+                label = int(labels[bw - pad, bl - pad, bh - pad])
+            for tri in tris:
+                ids = []
+                for e in tri:
+                    i, j = EDGES[e]
+                    code = tet[j] - tet[i]                 # the corners of a tetrahedron are nested: j adds axes to i
+                    ids.append(vertex_id[pts[i] + (code,)])
+                if MIRRORED[t]:
+                    ids = [ids[0], ids[2], ids[1]]
+                faces.append(ids)
+                flabels.append(label)
     return {"vertices": vertices, "faces": np.asarray(faces, np.int32).reshape(-1, 3),
             "colors": colors, "face_labels": np.asarray(flabels, np.uint8) if want_face_labels else None,
             "owners": np.asarray(owners, np.int64).reshape(-1, 4), "t": tvals, "g": g, "pos": pos}

@@ -123,6 +123,33 @@ def test_kernels_equal_the_restatement_on_a_sphere():
     assert 0.98 < vol / (4.0 / 3.0 * np.pi * 0.6 ** 3) < 1.0
 
 
+def test_scan_carries_across_three_chunks_of_workgroups():
+    """(131100, 2, 2) without the cap: 524400 points, 2049 workgroups of 256, so k_mesh_scan walks three chunks of 1024
+    and carries both prefixes twice.  A sparse field (isolated inside points every 997 steps along W and on both sides of
+    the points 262144 and 524288, where workgroups 1024 and 2048 begin) owns vertices and cells in every chunk and in the
+    workgroups next to each chunk boundary."""
+    shape = (131100, 2, 2)
+    n_points = int(np.prod(shape))
+    assert (n_points + 255) // 256 == 2049 > 2048
+    rng = np.random.default_rng(11)
+    field = (-0.1 - np.abs(rng.normal(size=shape))).astype(np.float32)
+    sites = sorted(set(range(3, shape[0] - 1, 997)) | {65534, 65535, 65536, 65537, 131070, 131071, 131072, 131073})
+    for k, w in enumerate(sites):
+        field[w, (k >> 1) & 1, k & 1] = np.float32(0.1 + abs(rng.normal()))
+    axes = _axes(shape)
+    ref = mr.marching_tetrahedra(field, 0.0, 0.75, axes, cap=False)
+    flat = lambda p: (p[:, 0] * shape[1] + p[:, 1]) * shape[2] + p[:, 2]                   # noqa: E731
+    owner_wg = flat(ref["owners"]) // 256
+    inside = ref["g"] >= 0
+    cnt = sum(inside[a:shape[0] - 1 + a, b:1 + b, c:1 + c].astype(int) for a in (0, 1) for b in (0, 1) for c in (0, 1))
+    cell_wg = flat(np.argwhere((cnt > 0) & (cnt < 8))) // 256
+    for wg in (owner_wg, cell_wg):
+        assert set(np.unique(wg // 1024)) == {0, 1, 2} and {1023, 1024, 2047, 2048} <= set(wg.tolist())
+    got = _gpu_mesh(field, 0.0, 0.75, axes, cap=False)
+    _assert_same(got, ref, "three scan chunks")
+    assert len(got["vertices"]) == len(ref["owners"]) > 500 and len(got["faces"]) == len(ref["faces"]) > 500
+
+
 def test_empty_result():
     field = np.full((6, 7, 8), -3.0, np.float32)
     got = _gpu_mesh(field, 0.0, 1.0, _axes(field.shape))
