@@ -2,7 +2,7 @@
 run as a script, the whole exact tier and tolerance tier on the library that INR_LIB_PATH names (a process binds one
 library): prints ``RESULT {"build": ..., "failures": [...], "ratios": {name: worst |got - ref| / cond}}``.
 
-Every buffer a kernel writes is a guarded view pre-filled with the NaN sentinel (``Buf`` of test_train_kernels); inputs
+Every buffer a kernel writes is a guarded view pre-filled with the NaN sentinel (``Buf`` of kernel_harness); inputs
 carry NaN guard words behind their last row; rows the instance launch must not read (m >= n, rays without a sample
 below n) hold NaN.  Only NaN poisons: every index in sample_ray stays in range."""
 import json
@@ -14,7 +14,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import field_backward_reference as R  # noqa: E402
-from test_train_kernels import Buf, check, cu_count, stream  # noqa: E402
+from kernel_harness import Buf, check, cu_count, finish, nan_out, pack_instance_device, pack_nerf_device, stream  # noqa: E402
 from train_kernels_reference import assert_same_bits  # noqa: E402
 
 F32 = np.float32
@@ -28,64 +28,43 @@ def zero_floats_for(i, M, cus):
     return (None, 4096, 1029, 2, 7, grid * 2048 + 4 * 77 + 1)[i % 6]
 
 
-def _out(*shape):
-    b = Buf(np.zeros(shape, F32))
-    b.fill_nan()
-    return b
-
-
 def _zero_buf(zero_floats):
-    return None if zero_floats is None else _out(zero_floats)
+    return None if zero_floats is None else nan_out(zero_floats)
 
 
 def _finish(bufs, zbuf, what):
-    import torch
-    torch.cuda.synchronize()
-    for k, b in bufs.items():
-        b.check_guards(f"{what} {k}")
+    """finish() of the harness, and the side buffer must hold zeros between intact guards."""
+    got = finish(dict(bufs, zero_buf=zbuf), what)
     if zbuf is not None:
-        assert_same_bits(zbuf.get(), np.zeros(zbuf.shape, F32), what + " zero_buf")
-        zbuf.check_guards(what + " zero_buf")
-
-
-def pack_nerf(lib, W):
-    wb = [Buf(np.asarray(w, F32)) for w in W]
-    pf, pb = _out(lib.inr_nerf_packed_floats()), _out(lib.inr_nerf_bwd_packed_floats())
-    check(lib.inr_nerf_pack_weights_device(*[b.ptr for b in wb], pf.ptr, pb.ptr, stream()), "nerf pack")
-    return pf, pb, wb
-
-
-def pack_instance(lib, W, K):
-    wb = [Buf(np.asarray(w, F32)) for w in W]
-    pf, pb = _out(lib.inr_instance_packed_floats(K)), _out(lib.inr_instance_bwd_packed_floats())
-    check(lib.inr_instance_pack_weights_device(*[b.ptr for b in wb], K, pf.ptr, pb.ptr, stream()), "instance pack")
-    return pf, pb, wb
+        assert_same_bits(got.pop("zero_buf"), np.zeros(zbuf.shape, F32), what + " zero_buf")
+    return got
 
 
 def run_nerf_head(lib, case, zero_floats=None, enc_dev=None):
     """inr_nerf_head_backward on ``case`` -> dict of numpy outputs (guards checked).  enc_dev: a device tensor to use
     instead of case["enc"]."""
     M = len(case["g_sigma"])
-    pf, pb, keep = pack_nerf(lib, case["W"])
+    pf, pb, keep = pack_nerf_device(lib, case["W"])
     enc = None if enc_dev is not None else Buf(np.asarray(case["enc"], F32))
     d, gs, gr = Buf(np.asarray(case["dirs"], F32)), Buf(np.asarray(case["g_sigma"], F32)), Buf(np.asarray(case["g_rgb"], F32))
-    o = {"d_enc": _out(M, 32), "gws0": _out(64, 32), "gws1": _out(16, 64), "gwc0": _out(64, 31), "gwc1": _out(64, 64),
-         "gwc2": _out(16, 64), "workspace": _out(lib.inr_instance_head_workspace_bytes() // 4)}
+    o = {"d_enc": nan_out(M, 32), "gws0": nan_out(64, 32), "gws1": nan_out(16, 64), "gwc0": nan_out(64, 31),
+         "gwc1": nan_out(64, 64), "gwc2": nan_out(16, 64),
+         "workspace": nan_out(lib.inr_instance_head_workspace_bytes() // 4)}
     z = _zero_buf(zero_floats)
     enc_ptr = enc.ptr if enc is not None else (enc_dev.data_ptr() if M else None)
     rc = lib.inr_nerf_head_backward(enc_ptr, d.ptr, gs.ptr, gr.ptr, M, float(case["density_scale"]), pf.ptr, pb.ptr,
                                     o["d_enc"].ptr, o["workspace"].ptr, o["gws0"].ptr, o["gws1"].ptr, o["gwc0"].ptr,
                                     o["gwc1"].ptr, o["gwc2"].ptr, None if z is None else z.ptr, zero_floats or 0, stream())
     check(rc, "nerf_head_backward")
-    _finish(o, z, "nerf_head")
-    del keep
-    return {k: b.get() for k, b in o.items() if k != "workspace"}
+    got = _finish(o, z, "nerf_head")
+    del keep, got["workspace"]
+    return got
 
 
 def run_instance_head(lib, case, zero_floats=None, enc_dev=None):
     M, K, N = len(case["wbuf"]), case["K"], case["N"]
     n = R.instance_rows(case)
-    pf, pb, keep = pack_instance(lib, case["W"], K)
+    pf, pb, keep = pack_instance_device(lib, case["W"], K)
     enc_h, wbuf, gp = np.array(case["enc"], F32), np.array(case["wbuf"], F32), np.array(case["g_pix"], F32)
     enc_h[n:], wbuf[n:] = NAN, NAN
     used = np.zeros(N, bool)
@@ -96,8 +75,8 @@ def run_instance_head(lib, case, zero_floats=None, enc_dev=None):
     n_dev = None if case["n"] is None else Buf(np.asarray([case["n"]], np.int32))
     sa = None if case["scale_a"] is None else Buf(np.asarray([case["scale_a"]], F32))
     sb = None if case["scale_b"] is None else Buf(np.asarray([case["scale_b"]], F32))
-    o = {"d_enc": _out(M, 32), "gw0": _out(64, 32), "gw1": _out(64, 64), "gw2": _out(K, 64),
-         "workspace": _out(lib.inr_instance_head_workspace_bytes() // 4)}
+    o = {"d_enc": nan_out(M, 32), "gw0": nan_out(64, 32), "gw1": nan_out(64, 64), "gw2": nan_out(K, 64),
+         "workspace": nan_out(lib.inr_instance_head_workspace_bytes() // 4)}
     z = _zero_buf(zero_floats)
     p = lambda b: None if b is None else b.ptr
     enc_ptr = enc.ptr if enc is not None else (enc_dev.data_ptr() if M else None)
@@ -105,36 +84,36 @@ def run_instance_head(lib, case, zero_floats=None, enc_dev=None):
                                         o["d_enc"].ptr, o["workspace"].ptr, o["gw0"].ptr, o["gw1"].ptr, o["gw2"].ptr, p(z),
                                         zero_floats or 0, stream())
     check(rc, "instance_head_backward")
-    _finish(o, z, "instance_head")
-    del keep
-    return {k: b.get() for k, b in o.items() if k != "workspace"}
+    got = _finish(o, z, "instance_head")
+    del keep, got["workspace"]
+    return got
 
 
 def run_nerf_chain(lib, case, saved):
     M = len(case["g_sigma"])
-    pf, pb, keep = pack_nerf(lib, case["W"])
+    pf, pb, keep = pack_nerf_device(lib, case["W"])
     gs, gr = Buf(np.asarray(case["g_sigma"], F32)), Buf(np.asarray(case["g_rgb"], F32))
     s = {k: Buf(np.asarray(saved[k], F32)) for k in ("rgb", "so", "h1", "c1", "c2")}
-    o = {"d_o": _out(M, 4), "dz_c2": _out(M, 64), "dz_c1": _out(M, 64), "d_so": _out(M, 16), "dz_h1": _out(M, 64),
-         "d_enc": _out(M, 32)}
+    o = {"d_o": nan_out(M, 4), "dz_c2": nan_out(M, 64), "dz_c1": nan_out(M, 64), "d_so": nan_out(M, 16), "dz_h1": nan_out(M, 64),
+         "d_enc": nan_out(M, 32)}
     check(lib.inr_nerf_backward(gs.ptr, gr.ptr, s["rgb"].ptr, s["so"].ptr, s["h1"].ptr, s["c1"].ptr, s["c2"].ptr, M,
                                 float(case["density_scale"]), pb.ptr, o["d_o"].ptr, o["dz_c2"].ptr, o["dz_c1"].ptr,
                                 o["d_so"].ptr, o["dz_h1"].ptr, o["d_enc"].ptr, stream()), "nerf_backward")
-    _finish(o, None, "nerf_chain")
+    got = finish(o, "nerf_chain")
     del keep, pf
-    return {k: b.get() for k, b in o.items()}
+    return got
 
 
 def run_instance_chain(lib, case, saved):
     M, K = len(saved["g"]), case["K"]
-    pf, pb, keep = pack_instance(lib, case["W"], K)
+    pf, pb, keep = pack_instance_device(lib, case["W"], K)
     g, h1, h2 = (Buf(np.asarray(saved[k], F32)) for k in ("g", "h1", "h2"))
-    o = {"dz2": _out(M, 64), "dz1": _out(M, 64), "denc": _out(M, 32)}
+    o = {"dz2": nan_out(M, 64), "dz1": nan_out(M, 64), "denc": nan_out(M, 32)}
     check(lib.inr_instance_backward(g.ptr, K, h1.ptr, h2.ptr, M, pb.ptr, o["dz2"].ptr, o["dz1"].ptr, o["denc"].ptr,
                                     stream()), "instance_backward")
-    _finish(o, None, "instance_chain")
+    got = finish(o, "instance_chain")
     del keep, pf
-    return {k: b.get() for k, b in o.items()}
+    return got
 
 
 def compare(prefix, case, size, got, ref, cond, build, ratios):

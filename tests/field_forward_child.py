@@ -3,7 +3,7 @@ template instantiation is reached whatever the Python layer would choose), and, 
 library that INR_LIB_PATH names (a process binds one library): prints ``RESULT {"build": ..., "failures": [...],
 "ratios": {output: worst |got - ref| / cond}}``.
 
-Every buffer a kernel writes is a guarded view pre-filled with the NaN sentinel (``Buf`` of test_train_kernels); inputs
+Every buffer a kernel writes is a guarded view pre-filled with the NaN sentinel (``Buf`` of kernel_harness); inputs
 carry NaN guard words on both sides.  Guards, and rows at or beyond the valid count, must keep their poison.  Host
 packers (inr_*_pack_weights, plain and fp16) serve the inference entry points, the device packers
 (inr_*_pack_weights_device) the training ones."""
@@ -17,26 +17,15 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import field_forward_reference as R  # noqa: E402
-from test_train_kernels import SENTINEL, Buf, check, stream  # noqa: E402
+from kernel_harness import Buf, check, finish, nan_out, pack_instance_device, pack_nerf_device, poisoned, stream  # noqa: E402
 from train_kernels_reference import assert_same_bits, bit_mismatches  # noqa: E402
 
 F32 = np.float32
 
 
-def _out(*shape):
-    b = Buf(np.zeros(shape, F32))
-    b.fill_nan()
-    return b
-
-
 def _sync():
     import torch
     torch.cuda.synchronize()
-
-
-def poisoned(a):
-    """Elementwise: the value is still the NaN sentinel the buffer was filled with."""
-    return np.ascontiguousarray(a, F32).view(np.int32) == SENTINEL
 
 
 class Dev:
@@ -58,9 +47,7 @@ def dev(table):
 
 def pack_nerf(lib, W, numerics=0, device=False):
     if device:
-        wb = [Buf(np.asarray(w, F32)) for w in W]
-        pf, pb = _out(lib.inr_nerf_packed_floats()), _out(lib.inr_nerf_bwd_packed_floats())
-        check(lib.inr_nerf_pack_weights_device(*[b.ptr for b in wb], pf.ptr, pb.ptr, stream()), "nerf pack")
+        pf, _, keep = pack_nerf_device(lib, W)
         _sync()
         return pf
     ws = [np.ascontiguousarray(w, F32) for w in W]
@@ -69,33 +56,24 @@ def pack_nerf(lib, W, numerics=0, device=False):
     return Buf(buf)
 
 
-def pack_instance(lib, W, K, device=False):
+def pack_instance(lib, W, K, device=False, numerics=0):
     if device:
-        wb = [Buf(np.asarray(w, F32)) for w in W]
-        pf, pb = _out(lib.inr_instance_packed_floats(K)), _out(lib.inr_instance_bwd_packed_floats())
-        check(lib.inr_instance_pack_weights_device(*[b.ptr for b in wb], K, pf.ptr, pb.ptr, stream()), "instance pack")
+        pf, _, keep = pack_instance_device(lib, W, K)
         _sync()
         return pf
     ws = [np.ascontiguousarray(w, F32) for w in W]
     buf = np.full(lib.inr_instance_packed_floats(K), np.nan, F32)
-    check(lib.inr_instance_pack_weights(*[w.ctypes.data for w in ws], K, buf.ctypes.data, 0), "instance pack")
+    check(lib.inr_instance_pack_weights(*[w.ctypes.data for w in ws], K, buf.ctypes.data, numerics), "instance pack")
     return Buf(buf)
-
-
-def _finish(bufs, what):
-    _sync()
-    for k, b in bufs.items():
-        b.check_guards(f"{what} {k}")
-    return {k: b.get() for k, b in bufs.items()}
 
 
 def ray_table(lib, o, d):
     """inr_ray_table_q -> (device rows [N,24], the SH rows [N,16] it holds); the origin and direction columns must echo
     the inputs bit for bit."""
     N = len(o)
-    ob, db, rt = Buf(np.asarray(o, F32)), Buf(np.asarray(d, F32)), _out(N, 24)
+    ob, db, rt = Buf(np.asarray(o, F32)), Buf(np.asarray(d, F32)), nan_out(N, 24)
     check(lib.inr_ray_table_q(ob.ptr, db.ptr, N, rt.ptr, stream()), "ray_table_q")
-    rows = _finish({"ray_table": rt}, "ray_table_q")["ray_table"]
+    rows = finish({"ray_table": rt}, "ray_table_q")["ray_table"]
     assert_same_bits(rows[:, 16:19], np.asarray(o, F32), "ray table origins")
     assert_same_bits(rows[:, 20:23], np.asarray(d, F32), "ray table directions")
     sh = rows[:, :16].reshape(N, 4, 4).transpose(0, 2, 1).reshape(N, 16)
@@ -121,19 +99,19 @@ def launch(lib, table, entry, M, D=None, W=None, n_dev=None, emb_key=None, numer
         mode, K = R.INSTANCE_ENTRIES[entry]
         packed = pack_instance(lib, W or R.instance_weights(table, K), K, device=mode != "")
         xb = Buf(R.plain_x(sc, bound) if x is None else x)
-        o = {"logits": _out(M, K)}
+        o = {"logits": nan_out(M, K)}
         if mode == "":
             rc = lib.inr_instance_forward(xb.ptr, M, nbp, bound, D.emb[0].ptr, D.desc, packed.ptr, K, o["logits"].ptr, s)
         elif mode == "_train":
-            o.update(ienc=_out(M, 32), ih1=_out(M, 64), ih2=_out(M, 64))
+            o.update(ienc=nan_out(M, 32), ih1=nan_out(M, 64), ih2=nan_out(M, 64))
             rc = lib.inr_instance_forward_train(xb.ptr, M, bound, D.emb[0].ptr, D.desc, packed.ptr, K, o["logits"].ptr,
                                                 o["ienc"].ptr, o["ih1"].ptr, o["ih2"].ptr, s)
         else:
-            o["ienc"] = _out(M, 32)
+            o["ienc"] = nan_out(M, 32)
             rc = lib.inr_instance_forward_enc(xb.ptr, M, nbp, bound, D.emb[0].ptr, D.desc, packed.ptr, K, o["logits"].ptr,
                                               o["ienc"].ptr, s)
         assert rc == expect_rc, (entry, rc)
-        return _finish(o, entry), None
+        return finish(o, entry), None
 
     feed, num_name = R.NERF_ENTRIES[entry][:2]
     numerics = R.NUMERICS[num_name] if numerics is None else numerics
@@ -143,30 +121,31 @@ def launch(lib, table, entry, M, D=None, W=None, n_dev=None, emb_key=None, numer
     emb = D.emb[ek].ptr
     if entry in ("fwd_rgb", "fwd_density", "fwd_o", "train", "enc"):
         xb, db = Buf(R.plain_x(sc, bound) if x is None else x), Buf(sc["dirs"])
-        o = {"sigma": _out(M)}
+        o = {"sigma": nan_out(M)}
         if entry != "fwd_density":
-            o["rgb"] = _out(M, 3)
+            o["rgb"] = nan_out(M, 3)
         if entry == "fwd_density":
-            o["geo"] = _out(M, 15)
+            o["geo"] = nan_out(M, 15)
         if entry.startswith("fwd"):
             rc = lib.inr_nerf_forward(xb.ptr, None if entry == "fwd_density" else db.ptr, M, nbp, bound, emb, D.desc,
                                       packed.ptr, ds, o["sigma"].ptr, o["rgb"].ptr if "rgb" in o else None,
                                       o["geo"].ptr if "geo" in o else None, numerics, s)
         elif entry == "train":
-            o.update(enc=_out(M, 32), h1=_out(M, 64), so=_out(M, 16), cin=_out(M, 32), c1=_out(M, 64), c2=_out(M, 64))
+            o.update(enc=nan_out(M, 32), h1=nan_out(M, 64), so=nan_out(M, 16), cin=nan_out(M, 32), c1=nan_out(M, 64),
+                     c2=nan_out(M, 64))
             rc = lib.inr_nerf_forward_train(xb.ptr, db.ptr, M, bound, emb, D.desc, packed.ptr, o["sigma"].ptr, o["rgb"].ptr,
                                             o["enc"].ptr, o["h1"].ptr, o["so"].ptr, o["cin"].ptr, o["c1"].ptr, o["c2"].ptr, s)
         else:
-            o["enc"] = _out(M, 32)
+            o["enc"] = nan_out(M, 32)
             rc = lib.inr_nerf_forward_enc(xb.ptr, db.ptr, M, bound, emb, D.desc, packed.ptr, o["sigma"].ptr, o["rgb"].ptr,
                                           o["enc"].ptr, s)
         if entry in ("train", "enc"):
             o["sigma1"] = o.pop("sigma")
     elif entry.startswith("table") or entry == "sliced":
         xb, rb, qb = Buf(sc["x01"]), Buf(sc["ray_ids"]), Buf(R.q_rows(sc["shrow"]))
-        o = {"sigma": _out(M), "rgb": _out(M, 3)}
+        o = {"sigma": nan_out(M), "rgb": nan_out(M, 3)}
         if entry == "sliced":
-            ws = _out(max(1, lib.inr_nerf_forward_table_sliced_workspace_bytes(M) // 4))
+            ws = nan_out(max(1, lib.inr_nerf_forward_table_sliced_workspace_bytes(M) // 4))
             rc = lib.inr_nerf_forward_table_sliced(xb.ptr, rb.ptr, qb.ptr, M, bound, emb, D.desc, packed.ptr, ds,
                                                    o["sigma"].ptr, o["rgb"].ptr, ws.ptr, s)
             _sync()
@@ -177,7 +156,7 @@ def launch(lib, table, entry, M, D=None, W=None, n_dev=None, emb_key=None, numer
     elif entry.startswith("records"):
         rt, sh_used = ray_table(lib, sc["o"], sc["d"])
         tb, rb = Buf(sc["t"]), Buf(sc["ray_ids"])
-        o = {"sigma": _out(M), "rgb": _out(M, 3)}
+        o = {"sigma": nan_out(M), "rgb": nan_out(M, 3)}
         old = os.environ.get("INR_FIELD_PAIR")
         if entry == "records_nopair":
             os.environ["INR_FIELD_PAIR"] = "0"
@@ -193,21 +172,21 @@ def launch(lib, table, entry, M, D=None, W=None, n_dev=None, emb_key=None, numer
     elif entry.startswith("dirs"):
         nd = int(entry[4:])
         xb, shb = Buf(R.plain_x(sc, bound) if x is None else x), Buf(R.sh_dirs_rows(table, nd))
-        o4 = _out(M, 4)
+        o4 = nan_out(M, 4)
         rc = lib.inr_nerf_forward_dirs(xb.ptr, M, bound, emb, D.desc, packed.ptr, shb.ptr, nd, o4.ptr, s)
         o = {"o4": o4}
     elif entry == "lattice":
         ax = R.lattice_axes(table, bound)
         axb, shb = [Buf(a) for a in ax], Buf(R.sh_dirs_rows(table, 3))
         Wn, Ln, Hn = (len(a) for a in ax)
-        o4 = _out(Wn, Ln, Hn, 4)
+        o4 = nan_out(Wn, Ln, Hn, 4)
         rc = lib.inr_nerf_forward_lattice(axb[0].ptr, axb[1].ptr, axb[2].ptr, Wn, Ln, Hn, bound, emb, D.desc, packed.ptr,
                                           shb.ptr, 3, R.LOGIT_MIN[R.tier_of(table)], o4.ptr, s)
         o = {"o4": o4}
     else:
         raise KeyError(entry)
     assert rc == expect_rc, (entry, rc)
-    got = _finish(o, entry)
+    got = finish(o, entry)
     if "o4" in got:
         o4 = got.pop("o4").reshape(-1, 4)
         got["rgbm"], got["logit"] = o4[:, :3], o4[:, 3]

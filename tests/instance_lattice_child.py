@@ -3,8 +3,8 @@ tests/test_instance_lattice_kernels.py, in the style of tests/field_forward_chil
 the lattice cases on the library that INR_LIB_PATH names (a process binds one library): prints ``RESULT {"build": ...,
 "failures": [...], "ratios": {output: worst |got - ref| as a fraction of its tolerance}}``.
 
-``labels`` is one byte per voxel, so it lives in a byte buffer of its own (``ByteBuf``) with GUARD_BYTES guard bytes on
-both sides, data and guards pre-filled with POISON_BYTE (no label: labels are < 64 or 255); confidence and density_logit
+``labels`` is one byte per voxel, so it lives in a byte buffer of its own (``ByteBuf`` of kernel_harness) with guard bytes
+on both sides, data and guards pre-filled with POISON_BYTE (no label: labels are < 64 or 255); confidence and density_logit
 are ``Buf`` views pre-filled with the NaN sentinel.  After a launch no poison may be left inside and every guard must be
 intact."""
 import functools
@@ -18,31 +18,9 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import field_forward_child as L  # noqa: E402
 import instance_lattice_reference as I  # noqa: E402
-from test_train_kernels import Buf, check, stream  # noqa: E402
+from kernel_harness import POISON_BYTE, SENTINEL, Buf, ByteBuf, check, finish, nan_out, poisoned, stream  # noqa: E402
 
 F32 = np.float32
-GUARD_BYTES, POISON_BYTE = 67, 0xA5          # an odd guard: the label pointer is not even 2-byte aligned
-
-
-class ByteBuf:
-    """n bytes between two runs of GUARD_BYTES guard bytes, everything POISON_BYTE."""
-
-    def __init__(self, n):
-        import torch
-        self.n = int(n)
-        self.whole = torch.full((2 * GUARD_BYTES + self.n,), POISON_BYTE, dtype=torch.uint8, device="cuda:0")
-        self.raw = self.whole[GUARD_BYTES:GUARD_BYTES + self.n]
-
-    @property
-    def ptr(self):
-        return self.whole.data_ptr() + GUARD_BYTES
-
-    def get(self):
-        return self.raw.cpu().numpy()
-
-    def check_guards(self, what=""):
-        head, tail = self.whole[:GUARD_BYTES], self.whole[GUARD_BYTES + self.n:]
-        assert bool((head == POISON_BYTE).all()) and bool((tail == POISON_BYTE).all()), f"{what}: a guard byte was written"
 
 
 @functools.lru_cache(maxsize=2)
@@ -67,27 +45,20 @@ def launch(lib, ref, sigma_thresh, want_logit=True, dims=None, expect_written=Tr
     N = W * Ln * H if expect_written else int(np.prod(ref.dims))
     axb = [Buf(a) for a in ref.ax]
     pn, pi = L.pack_nerf(lib, ref.Wn, 0), pack_instance(lib, ref.Wi, ref.K)
-    lab, conf = ByteBuf(N), L._out(N)
-    logit = L._out(N) if want_logit else None
+    lab, conf = ByteBuf(N), nan_out(N)
+    logit = nan_out(N) if want_logit else None
     rc = lib.inr_instance_lattice(axb[0].ptr, axb[1].ptr, axb[2].ptr, W, Ln, H, ref.bound, Dn.emb[0].ptr, Dn.desc, pn.ptr,
                                   float(F32(ref.ds)), float(F32(sigma_thresh)), Di.emb[0].ptr, Di.desc, pi.ptr, ref.K, lab.ptr,
                                   conf.ptr, logit.ptr if want_logit else None, stream())
     check(rc, "instance_lattice")
-    L._sync()
-    lab.check_guards("labels")
-    conf.check_guards("confidence")
-    if want_logit:
-        logit.check_guards("density_logit")
-    out = lab.get(), conf.get(), logit.get() if want_logit else None
-    for name, a in zip(("labels", "confidence", "density_logit"), out):
-        if a is None:
-            continue
-        left = (a == POISON_BYTE) if name == "labels" else L.poisoned(a)
+    got = finish(dict(labels=lab, confidence=conf, density_logit=logit), "instance_lattice")
+    for name, a in got.items():
+        left = (a == POISON_BYTE) if name == "labels" else poisoned(a)
         if expect_written:
             assert not left.any(), f"{name}: {int(left.sum())} of {N} voxels were not written"
         else:
             assert left.all(), f"{name}: an empty lattice wrote something"
-    return out
+    return got["labels"], got["confidence"], got.get("density_logit")
 
 
 def run_case(lib, case, build, ratios, null_logit_on="q90"):
@@ -110,19 +81,15 @@ def launch_stats(lib, lab, conf, K):
         import torch
         lb.raw.copy_(torch.from_numpy(np.ascontiguousarray(lab).reshape(-1)))
     cb = Buf(np.ascontiguousarray(conf, F32).reshape(-1) if N else np.zeros(1, F32))
-    ws = L._out(lib_workspace_words())
-    counts, boxes, sums = (Buf(np.zeros(s, t)) for s, t in (((64,), np.int32), ((64, 6), np.int32), ((64,), F32)))
-    for b in (counts, boxes, sums):
-        b.fill_nan()
+    ws = nan_out(lib_workspace_words())
+    counts, boxes, sums = nan_out(64, dtype=np.int32), nan_out(64, 6, dtype=np.int32), nan_out(64)
     check(lib.inr_instance_volume_stats(lb.ptr, cb.ptr, W, Ln, H, K, ws.ptr, lib_workspace_words() * 4, counts.ptr, boxes.ptr,
                                         sums.ptr, stream()), "instance_volume_stats")
-    L._sync()
-    lb.check_guards("labels")
-    for name, b in (("confidence", cb), ("workspace", ws), ("counts", counts), ("boxes", boxes), ("conf_sum", sums)):
-        b.check_guards(name)
-    c, bx, s = counts.get(), boxes.get(), sums.get()
-    assert (c[K:] == L.SENTINEL).all() and (bx[K:] == L.SENTINEL).all() and L.poisoned(s[K:]).all(), "an entry beyond K was written"
-    assert not (c[:K] == L.SENTINEL).any() and not (bx[:K] == L.SENTINEL).any() and not L.poisoned(s[:K]).any()
+    got = finish(dict(labels=lb, confidence=cb, workspace=ws, counts=counts, boxes=boxes, conf_sum=sums),
+                 "instance_volume_stats")
+    c, bx, s = got["counts"], got["boxes"], got["conf_sum"]
+    assert (c[K:] == SENTINEL).all() and (bx[K:] == SENTINEL).all() and poisoned(s[K:]).all(), "an entry beyond K was written"
+    assert not (c[:K] == SENTINEL).any() and not (bx[:K] == SENTINEL).any() and not poisoned(s[:K]).any()
     return c[:K], bx[:K], s[:K]
 
 

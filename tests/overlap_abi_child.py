@@ -2,67 +2,48 @@
 valid except the one named and prints one JSON object {"<name>:<case>": [return code, message]}.  Validation precedes
 every launch, so this runs on a CPU-only box; a crash ends the process without the final line."""
 import ctypes
-import json
 import os
 import sys
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from instance_nerf_amd import _lib  # noqa: E402
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_probe as A  # noqa: E402
 
-lib = _lib.load()
-HOST = ctypes.create_string_buffer(1 << 16)
-ADDR = (ctypes.addressof(HOST) + 255) // 256 * 256
-
-# argument positions (include/inr.h)
-MASKS = dict(masks=0, k=1, V=2, planes=3, area=4)
-LABELS = dict(labels=0, V=1, K=2, first_channel=3, planes=4, area=5)
-OVERLAP = dict(planes_a=0, kA=1, planes_b=2, kB=3, V=4, run_words=5, inter=6)
+ADDR = A.ADDR
+MASKS, LABELS, OVERLAP = "inr_pack_mask_planes", "inr_pack_label_planes", "inr_mask_overlap"
+BASE = {MASKS: {}, LABELS: dict(first_channel=1), OVERLAP: dict(run_words=0)}
 
 
-def call(name, pos, **over):
-    _, argtypes = _lib._SIGS[name]
-    args = [ctypes.c_void_p(ADDR) if t is _lib.P else 4 for t in argtypes]
-    if "run_words" in pos:
-        args[pos["run_words"]] = 0
-    if "first_channel" in pos:
-        args[pos["first_channel"]] = 1
-    for key, v in over.items():
-        args[pos[key]] = v
-    rc = int(getattr(lib, name)(*args))
-    msg = lib.inr_last_error()
-    return [rc, msg.decode() if msg else ""]
+def call(name, **over):
+    return A.call(name, A.default_args(name, ints=4), **dict(BASE[name], **over))
 
 
 out = {}
-for name, pos in (("inr_pack_mask_planes", MASKS), ("inr_pack_label_planes", LABELS), ("inr_mask_overlap", OVERLAP)):
-    out[f"{name}:V_zero"] = call(name, pos, V=0)
-    out[f"{name}:V_negative"] = call(name, pos, V=-1)
-    out[f"{name}:V_2_31"] = call(name, pos, V=1 << 31)
-    out[f"{name}:V_2_40"] = call(name, pos, V=1 << 40)
-    if name != "inr_mask_overlap":
-        out[f"{name}:planes_null"] = call(name, pos, planes=None)
-        out[f"{name}:area_null"] = call(name, pos, area=None)
-        out[f"{name}:planes_misaligned"] = call(name, pos, planes=ctypes.c_void_p(ADDR + 4))
-out["inr_pack_mask_planes:k_negative"] = call("inr_pack_mask_planes", MASKS, k=-1)
-out["inr_pack_mask_planes:k_1025"] = call("inr_pack_mask_planes", MASKS, k=1025)
-out["inr_pack_mask_planes:masks_null"] = call("inr_pack_mask_planes", MASKS, masks=None)
-out["inr_pack_mask_planes:k_zero_null_ok"] = call("inr_pack_mask_planes", MASKS, k=0, masks=None, planes=None, area=None)
-out["inr_pack_label_planes:K_zero"] = call("inr_pack_label_planes", LABELS, K=0)
-out["inr_pack_label_planes:K_257"] = call("inr_pack_label_planes", LABELS, K=257)
-out["inr_pack_label_planes:first_channel_negative"] = call("inr_pack_label_planes", LABELS, first_channel=-1)
-out["inr_pack_label_planes:first_channel_above_K"] = call("inr_pack_label_planes", LABELS, first_channel=5)
-out["inr_pack_label_planes:labels_null"] = call("inr_pack_label_planes", LABELS, labels=None)
-out["inr_pack_label_planes:first_channel_K_null_ok"] = call("inr_pack_label_planes", LABELS, first_channel=4, planes=None,
-                                                            area=None)
+for name in (MASKS, LABELS, OVERLAP):
+    out[f"{name}:V_zero"] = call(name, V=0)
+    out[f"{name}:V_negative"] = call(name, V=-1)
+    out[f"{name}:V_2_31"] = call(name, V=1 << 31)
+    out[f"{name}:V_2_40"] = call(name, V=1 << 40)
+    if name != OVERLAP:
+        out[f"{name}:planes_null"] = call(name, planes=None)
+        out[f"{name}:area_null"] = call(name, area=None)
+        out[f"{name}:planes_misaligned"] = call(name, planes=ctypes.c_void_p(ADDR + 4))
+out[f"{MASKS}:k_negative"] = call(MASKS, k=-1)
+out[f"{MASKS}:k_1025"] = call(MASKS, k=1025)
+out[f"{MASKS}:masks_null"] = call(MASKS, masks=None)
+out[f"{MASKS}:k_zero_null_ok"] = call(MASKS, k=0, masks=None, planes=None, area=None)
+out[f"{LABELS}:K_zero"] = call(LABELS, K=0)
+out[f"{LABELS}:K_257"] = call(LABELS, K=257)
+out[f"{LABELS}:first_channel_negative"] = call(LABELS, first_channel=-1)
+out[f"{LABELS}:first_channel_above_K"] = call(LABELS, first_channel=5)
+out[f"{LABELS}:labels_null"] = call(LABELS, labels=None)
+out[f"{LABELS}:first_channel_K_null_ok"] = call(LABELS, first_channel=4, planes=None, area=None)
 for side in ("kA", "kB"):
-    out[f"inr_mask_overlap:{side}_negative"] = call("inr_mask_overlap", OVERLAP, **{side: -1})
-    out[f"inr_mask_overlap:{side}_1025"] = call("inr_mask_overlap", OVERLAP, **{side: 1025})
-    out[f"inr_mask_overlap:{side}_zero_null_ok"] = call("inr_mask_overlap", OVERLAP, **{side: 0}, planes_a=None, planes_b=None,
-                                                         inter=None)
-out["inr_mask_overlap:run_words_100"] = call("inr_mask_overlap", OVERLAP, run_words=100)
-out["inr_mask_overlap:run_words_negative"] = call("inr_mask_overlap", OVERLAP, run_words=-256)
-out["inr_mask_overlap:planes_a_null"] = call("inr_mask_overlap", OVERLAP, planes_a=None)
-out["inr_mask_overlap:planes_b_misaligned"] = call("inr_mask_overlap", OVERLAP, planes_b=ctypes.c_void_p(ADDR + 4))
-out["inr_mask_overlap:inter_null"] = call("inr_mask_overlap", OVERLAP, inter=None)
-out["alive"] = [0, "reached the end"]
-sys.stdout.write(json.dumps(out) + "\n")
+    out[f"{OVERLAP}:{side}_negative"] = call(OVERLAP, **{side: -1})
+    out[f"{OVERLAP}:{side}_1025"] = call(OVERLAP, **{side: 1025})
+    out[f"{OVERLAP}:{side}_zero_null_ok"] = call(OVERLAP, **{side: 0}, planes_a=None, planes_b=None, inter=None)
+out[f"{OVERLAP}:run_words_100"] = call(OVERLAP, run_words=100)
+out[f"{OVERLAP}:run_words_negative"] = call(OVERLAP, run_words=-256)
+out[f"{OVERLAP}:planes_a_null"] = call(OVERLAP, planes_a=None)
+out[f"{OVERLAP}:planes_b_misaligned"] = call(OVERLAP, planes_b=ctypes.c_void_p(ADDR + 4))
+out[f"{OVERLAP}:inter_null"] = call(OVERLAP, inter=None)
+A.emit(out)

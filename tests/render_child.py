@@ -1,5 +1,5 @@
 """Launches of inr_nerf_render and inr_instance_render through the C ABI for tests/test_render_kernels.py, on plain
-device buffers with guard words (``Buf`` of test_train_kernels; every output pre-filled with the NaN sentinel), and the
+device buffers with guard words (``Buf`` of kernel_harness; every output pre-filled with the NaN sentinel), and the
 comparisons with tests/render_reference.py.  Run as a script: both tiers at the small sizes on the library that
 INR_LIB_PATH names (a process binds one library); prints ``RESULT {"build": ..., "failures": [...], "ratios": {...}}``."""
 import json
@@ -14,7 +14,7 @@ import composite_reference as C  # noqa: E402
 import field_forward_child as L  # noqa: E402
 import field_forward_reference as R  # noqa: E402
 import render_reference as X  # noqa: E402
-from test_train_kernels import Buf  # noqa: E402
+from kernel_harness import Buf, finish, nan_out, poisoned, stream  # noqa: E402
 from train_kernels_reference import bit_mismatches  # noqa: E402
 
 F32 = np.float32
@@ -43,15 +43,15 @@ def launch_nerf(lib, case, M=None, numerics=0, weights=True, x_is_01=0):
     packed = L.pack_nerf(lib, W, numerics)
     xb, db = _positions(case, x_is_01), Buf(C.to_patch(case["deltas"], case["slots"], total))
     rb, rdb = Buf(rays), Buf(case["rays_d"])
-    o = {"weights_sum": L._out(N), "depth": L._out(N), "image": L._out(N, 3)}
+    o = {"weights_sum": nan_out(N), "depth": nan_out(N), "image": nan_out(N, 3)}
     if weights:
-        o["weights"] = L._out(total)
+        o["weights"] = nan_out(total)
     ev = Buf(np.zeros(2 * (1 + N_CURSORS), np.int32))
     rc = lib.inr_nerf_render(xb.ptr, db.ptr, rb.ptr, rdb.ptr, N, M, case["bound"], D.emb[numerics & 1].ptr, D.desc,
                              packed.ptr, case["ds"], case["T"], o["weights_sum"].ptr, o["depth"].ptr, o["image"].ptr,
-                             o["weights"].ptr if weights else None, ev.ptr, x_is_01, numerics, L.stream())
+                             o["weights"].ptr if weights else None, ev.ptr, x_is_01, numerics, stream())
     assert rc == 0, rc
-    got = L._finish(dict(o, evaluated=ev), "nerf_render")
+    got = finish(dict(o, evaluated=ev), "nerf_render")
     got["evaluated"] = int(got["evaluated"].view(np.uint64)[0])
     return got
 
@@ -62,21 +62,13 @@ def launch_instance(lib, case, K, w_patch, M=None, numerics=0, x_is_01=0):
     N, total = len(rays), _total(case)
     M = total if M is None else int(M)
     D = L.dev(case["table"])
-    packed = L.pack_instance(lib, R.instance_weights(case["table"], K), K) if not numerics & 2 else \
-        pack_instance_f16(lib, R.instance_weights(case["table"], K), K)
+    packed = L.pack_instance(lib, R.instance_weights(case["table"], K), K, numerics=numerics & 2)
     xb, wb, rb = _positions(case, x_is_01), Buf(np.asarray(w_patch, F32)), Buf(rays)
-    out, cur = L._out(N, K), Buf(np.zeros(2 * N_CURSORS, np.int32))
+    out, cur = nan_out(N, K), Buf(np.zeros(2 * N_CURSORS, np.int32))
     rc = lib.inr_instance_render(xb.ptr, rb.ptr, wb.ptr, N, M, case["bound"], D.emb[numerics & 1].ptr, D.desc, packed.ptr,
-                                 K, out.ptr, x_is_01, cur.ptr, numerics, L.stream())
+                                 K, out.ptr, x_is_01, cur.ptr, numerics, stream())
     assert rc == 0, rc
-    return L._finish({"out": out, "cursors": cur}, "instance_render")["out"]
-
-
-def pack_instance_f16(lib, W, K):
-    ws = [np.ascontiguousarray(w, F32) for w in W]
-    buf = np.full(lib.inr_instance_packed_floats(K), np.nan, F32)
-    L.check(lib.inr_instance_pack_weights(*[w.ctypes.data for w in ws], K, buf.ctypes.data, 2), "instance pack")
-    return Buf(buf)
+    return finish({"out": out, "cursors": cur}, "instance_render")["out"]
 
 
 def _bits(name, got, want):
@@ -99,7 +91,7 @@ def compare_exact(name, got, ref):
     if got.get("weights") is not None:
         wr = ref["written"]
         fails += _bits(f"{name}.weights", got["weights"][wr], ref["weights"][wr])
-        if not L.poisoned(got["weights"][~wr]).all():
+        if not poisoned(got["weights"][~wr]).all():
             fails.append(f"{name}.weights: a row of a dropped group or beyond M was written")
     if got["evaluated"] != ref["evaluated"]:
         fails.append(f"{name}.evaluated: {got['evaluated']} != {ref['evaluated']}")

@@ -2,54 +2,31 @@
 named and prints one JSON object {"<name>:<case>": [return code, message]}.  Validation precedes every launch, so this
 runs on a CPU-only box; a crash ends the process without the final line."""
 import ctypes
-import json
 import os
 import sys
 
 import numpy as np
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_probe as A  # noqa: E402
 from instance_nerf_amd import _lib, metrics  # noqa: E402
 
 lib = _lib.load()
-HOST = ctypes.create_string_buffer(1 << 16)
-ADDR = (ctypes.addressof(HOST) + 255) // 256 * 256
+ADDR = A.ADDR
 WINDOW = metrics.gaussian_window()
 NAN_WINDOW = WINDOW.copy()
 NAN_WINDOW[3] = np.nan
-
-# argument positions (include/inr.h)
-POS = dict(pred=0, truth=1, B=2, H=3, W=4, C=5, window=6, data_range=7, out_ssim=8, out_sse=9, out_map=10, workspace=11,
-           workspace_bytes=12, stream=13)
-B, H, W, C = 2, 40, 100, 3
-
-
-def last_error():
-    msg = lib.inr_last_error()
-    return msg.decode() if msg else ""
+SHAPE = dict(B=2, H=40, W=100, C=3)
 
 
 def forward(**over):
     """All pointers into the host buffer, a valid shape and the workspace size the library asks for; `over` replaces
     arguments by name (shape arguments before the workspace size is taken, unless that is given too)."""
-    shape = dict(B=B, H=H, W=W, C=C)
-    shape.update({k: v for k, v in over.items() if k in shape})
+    shape = dict(SHAPE, **{k: v for k, v in over.items() if k in SHAPE})
     need = lib.inr_ssim_workspace_bytes(shape["B"], shape["H"], shape["W"], shape["C"])
-    args = [ctypes.c_void_p(ADDR)] * 14
-    for k, v in shape.items():
-        args[POS[k]] = v
-    args[POS["window"]] = WINDOW.ctypes.data_as(ctypes.c_void_p)
-    args[POS["workspace_bytes"]] = max(int(need), 16)
-    args[POS["stream"]] = None
-    for k, v in over.items():
-        args[POS[k]] = v(need) if callable(v) else v
-    rc = int(lib.inr_ssim_forward(*args))
-    return [rc, last_error()]
-
-
-def size(*shape):
-    rc = int(lib.inr_ssim_workspace_bytes(*shape))
-    return [rc, last_error()]
+    base = dict(shape, window11=WINDOW.ctypes.data_as(ctypes.c_void_p), workspace_bytes=max(int(need), 16), s=None)
+    base.update({k: v(need) if callable(v) else v for k, v in over.items()})
+    return A.call("inr_ssim_forward", A.default_args("inr_ssim_forward"), **base)
 
 
 out = {}
@@ -61,14 +38,14 @@ out["inr_ssim_forward:B_0"] = forward(B=0)
 out["inr_ssim_forward:too_large"] = forward(B=4, H=1 << 14, W=1 << 14, C=2)
 out["inr_ssim_forward:workspace_one_byte_short"] = forward(workspace_bytes=lambda need: need - 1)
 out["inr_ssim_forward:workspace_misaligned"] = forward(workspace=ctypes.c_void_p(ADDR + 4))
-for name in ("pred", "workspace", "window", "data_range", "out_ssim"):
-    out[f"inr_ssim_forward:{name}_null"] = forward(**{name: None})
-out["inr_ssim_forward:window_nan"] = forward(window=NAN_WINDOW.ctypes.data_as(ctypes.c_void_p))
-out["inr_ssim_workspace_bytes:C_5"] = size(1, 40, 40, 5)
-out["inr_ssim_workspace_bytes:H_10"] = size(1, 10, 40, 3)
-out["inr_ssim_workspace_bytes:W_negative"] = size(1, 40, -1, 3)
-out["inr_ssim_workspace_bytes:too_large"] = size(4, 1 << 14, 1 << 14, 2)
+for label, name in (("pred", "pred"), ("workspace", "workspace"), ("window", "window11"), ("data_range", "data_range_dev"),
+                    ("out_ssim", "out_ssim")):
+    out[f"inr_ssim_forward:{label}_null"] = forward(**{name: None})
+out["inr_ssim_forward:window_nan"] = forward(window11=NAN_WINDOW.ctypes.data_as(ctypes.c_void_p))
+out["inr_ssim_workspace_bytes:C_5"] = A.size_query("inr_ssim_workspace_bytes", 1, 40, 40, 5)
+out["inr_ssim_workspace_bytes:H_10"] = A.size_query("inr_ssim_workspace_bytes", 1, 10, 40, 3)
+out["inr_ssim_workspace_bytes:W_negative"] = A.size_query("inr_ssim_workspace_bytes", 1, 40, -1, 3)
+out["inr_ssim_workspace_bytes:too_large"] = A.size_query("inr_ssim_workspace_bytes", 4, 1 << 14, 1 << 14, 2)
 for shape in ((1, 11, 11, 1), (3, 26, 74, 4), (1, 27, 75, 3), (8, 800, 800, 3)):
     out["size:" + "x".join(map(str, shape))] = int(lib.inr_ssim_workspace_bytes(*shape))
-out["alive"] = [0, "reached the end"]
-sys.stdout.write(json.dumps(out) + "\n")
+A.emit(out)

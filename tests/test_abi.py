@@ -1,8 +1,12 @@
 """The C-ABI library loads on a CPU-only box and exports every symbol include/inr.h declares."""
 import os
 import re
+import sys
 
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_probe  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -18,17 +22,20 @@ def test_header_and_binding_agree():
     assert sorted(_lib.EXPORTS) == _declared()
 
 
-def _prototypes():
-    """name -> list of parameter type strings, parsed from the header."""
-    src = open(os.path.join(ROOT, "include", "inr.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"//[^\n]*", "", src)
-    out = {}
-    for m in re.finditer(r"\b(?:int|int64_t|const char\*)\s+(inr_[a-zA-Z0-9_]+)\s*\(([^;{]*?)\)\s*;", src, flags=re.S):
-        args = " ".join(m.group(2).split())
-        params = [] if args in ("", "void") else [a.strip() for a in args.split(",")]
-        out[m.group(1)] = params
-    return out
+def test_every_parameter_of_the_header_has_a_name_of_its_own():
+    """The bad-argument children address arguments by these names (tests/abi_probe.py): per export non-empty
+    identifiers, unique within the prototype, as many as the binding's argtypes - and no trailing comment such as
+    /*nullable*/ or /*[G,6]*/ in one."""
+    from instance_nerf_amd import _lib
+    protos = abi_probe.prototypes()
+    assert sorted(protos) == _declared()
+    for name, params in protos.items():
+        names = [n for _, n in params]
+        assert all(re.fullmatch(r"[A-Za-z_][A-Za-z0-9_]*", n) for n in names), (name, names)
+        assert len(set(names)) == len(names) == len(_lib._SIGS[name][1]), (name, names)
+        assert not any(n in ("nullable", "const", "float", "int", "int32_t", "int64_t", "void") for n in names), (name, names)
+    with pytest.raises(KeyError, match="inr_set_march_mode has no parameter 'modus'"):      # before any call is made
+        abi_probe.call("inr_set_march_mode", [0], modus=1)
 
 
 def test_ctypes_signatures_match_the_header():
@@ -36,7 +43,7 @@ def test_ctypes_signatures_match_the_header():
     parameters sit where the header puts them (a wrong ctypes width corrupts arguments silently)."""
     import ctypes
     from instance_nerf_amd import _lib
-    protos = _prototypes()
+    protos = {name: [f"{decl} {n}" for decl, n in params] for name, params in abi_probe.prototypes().items()}
     assert sorted(protos) == _declared()
     ptr_like = (ctypes.c_void_p, ctypes.c_char_p)
     for name, params in protos.items():

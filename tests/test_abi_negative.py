@@ -5,12 +5,13 @@ names a limit - with K > 64, 17 levels, misaligned buffers, too many tensors: ea
 INR_EINVAL and a message from inr_last_error(), and the process must still be alive afterwards.  The library loads on
 a CPU-only box and validation precedes every launch, so this is a CPU test; the calls run in a child process so that a
 crash is a test failure, not the end of the test session."""
-import json
 import os
-import subprocess
 import sys
 
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_probe  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL, ELAUNCH, ENODEV = -1, -2, -3
@@ -26,17 +27,7 @@ NO_BAD_VALUE = set()
 
 @pytest.fixture(scope="module")
 def results():
-    from instance_nerf_amd import _lib, build
-    if not os.path.exists(_lib.LIB_PATH):
-        build.build(verbose=False)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "abi_negative_child.py")], capture_output=True, text=True,
-                       timeout=600, env=dict(os.environ, HIP_VISIBLE_DEVICES=os.environ.get("HIP_VISIBLE_DEVICES", "")))
-    assert r.returncode == 0, f"the child died (rc {r.returncode}): an export crashed on bad arguments\n{r.stderr[-2000:]}"
-    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
-    assert lines, r.stdout[-1000:]
-    out = json.loads(lines[-1])
-    assert out["alive"] == [0, "reached the end"]
-    return out
+    return abi_probe.run_abi_child("abi_negative_child.py", env=abi_probe.NO_GPU)
 
 
 def test_every_export_is_covered(results):
@@ -119,7 +110,6 @@ def test_a_launch_that_cannot_succeed_returns_a_code():
     import torch
     if torch.cuda.is_available():
         pytest.skip("GPU present: the launch-failure case of a GPU box is test_gpu_parity.py::test_launch_failure_is_a_return_code")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "abi_negative_child.py")], capture_output=True, text=True, timeout=600)
-    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    out = abi_probe.run_abi_child("abi_negative_child.py")
     rc, msg = out["inr_nerf_pack_weights_device:launch"]
     assert rc == ELAUNCH and msg, (rc, msg)

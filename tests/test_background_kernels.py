@@ -31,7 +31,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import background_reference as br  # noqa: E402
-from test_train_kernels import SENTINEL, Buf, check, stream  # noqa: E402
+from kernel_harness import SENTINEL, Buf, check, nan_out, stream  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 f32, f64 = np.float32, np.float64
@@ -49,12 +49,6 @@ def lib():
 def desc(name):
     from instance_nerf_amd import _lib
     return _lib.make_grid_desc(br.table(name))
-
-
-def nan_buf(shape):
-    b = Buf(np.zeros(shape, f32))
-    b.fill_nan()
-    return b
 
 
 def close(got, want64, tol, what):
@@ -75,7 +69,7 @@ def same_bits(got, want, what):
 
 def device_coords(lib, o, d):
     N = o.shape[0]
-    O, D, C = Buf(o), Buf(d), nan_buf((N, 2))
+    O, D, C = Buf(o), Buf(d), nan_out(N, 2)
     check(lib.inr_sph_from_ray(O.ptr, D.ptr, N, br.RADIUS, C.ptr, stream()), "sph_from_ray")
     C.check_guards("sph_from_ray coords")
     return C.get()
@@ -119,7 +113,7 @@ def test_grid2d_forward_and_the_rows_a_sample_touches(lib, name):
             check(lib.inr_grid2d_encode_forward(None, E.ptr, desc(name), 0, 1.0, None, stream()))
             check(lib.inr_grid2d_encode_backward(None, None, desc(name), 0, 1.0, None, stream()))
             continue
-        X, OUT = Buf(x[:M]), nan_buf((M, 2 * L))
+        X, OUT = Buf(x[:M]), nan_out(M, 2 * L)
         check(lib.inr_grid2d_encode_forward(X.ptr, E.ptr, desc(name), M, 1.0, OUT.ptr, stream()), "grid2d forward")
         OUT.check_guards("grid2d forward")
         got = OUT.get()
@@ -180,7 +174,7 @@ def test_background_forward(lib, name):
             continue
         o, d, miss = br.rays(N)
         coords = device_coords(lib, o, d)
-        O, D, BG, CO = Buf(o), Buf(d), nan_buf((N, 3)), nan_buf((N, 2))
+        O, D, BG, CO = Buf(o), Buf(d), nan_out(N, 3), nan_out(N, 2)
         check(lib.inr_background_forward(O.ptr, D.ptr, N, br.RADIUS, E.ptr, desc(name), W0.ptr, W1.ptr, BG.ptr, CO.ptr, None,
                                          None, stream()), "background_forward")
         for b in (BG, CO):
@@ -193,7 +187,7 @@ def test_background_forward(lib, name):
         # the in-place blend; without coords_out
         rng = np.random.default_rng(13 + N)
         ws, img = rng.uniform(0, 1, N).astype(f32), rng.uniform(0, 1, (N, 3)).astype(f32)
-        WS, IMG, BG2 = Buf(ws), Buf(img), nan_buf((N, 3))
+        WS, IMG, BG2 = Buf(ws), Buf(img), nan_out(N, 3)
         check(lib.inr_background_forward(O.ptr, D.ptr, N, br.RADIUS, E.ptr, desc(name), W0.ptr, W1.ptr, BG2.ptr, None, WS.ptr,
                                          IMG.ptr, stream()), "background_forward (blend)")
         for b in (WS, IMG, BG2):
@@ -222,8 +216,8 @@ def test_background_backward(lib, name):
         O, D, G = Buf(o), Buf(d), Buf(g)
         runs = []
         for _ in range(2):
-            GE, GW0, GW1 = Buf(np.zeros((T, 2), f32)), nan_buf((64, 24)), nan_buf((3, 64))
-            WSP = nan_buf((lib.inr_background_workspace_bytes(N) // 4,))
+            GE, GW0, GW1 = Buf(np.zeros((T, 2), f32)), nan_out(64, 24), nan_out(3, 64)
+            WSP = nan_out(lib.inr_background_workspace_bytes(N) // 4)
             check(lib.inr_background_backward(G.ptr, O.ptr, D.ptr, N, br.RADIUS, E.ptr, desc(name), W0.ptr, W1.ptr, GE.ptr,
                                               GW0.ptr, GW1.ptr, WSP.ptr, stream()), "background_backward")
             for b in (GE, GW0, GW1, WSP):
@@ -238,7 +232,7 @@ def test_background_backward(lib, name):
         # against the composable chain: inr_grid2d_encode_forward and inr_sh_encode_forward of the same coordinates and
         # directions, the two layers and the sigmoid as torch ops, autograd back to the encoder output, and that encoder
         # gradient through inr_grid2d_encode_backward
-        X, ENC, SH = Buf(coords), nan_buf((N, 8)), nan_buf((N, 16))
+        X, ENC, SH = Buf(coords), nan_out(N, 8), nan_out(N, 16)
         check(lib.inr_grid2d_encode_forward(X.ptr, E.ptr, desc(name), N, 1.0, ENC.ptr, stream()), "grid2d forward")
         check(lib.inr_sh_encode_forward(D.ptr, N, 4, SH.ptr, stream()), "sh forward")
         enc = ENC.t.clone().requires_grad_(True)

@@ -25,7 +25,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import box_targets_cases as bc  # noqa: E402
 import box_targets_reference as br  # noqa: E402
-from test_train_kernels import DEV, Buf, check, stream  # noqa: E402
+from kernel_harness import DEV, Buf, check, stream  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 i32, f32 = np.int32, np.float32

@@ -3,11 +3,9 @@ composable path of instance_nerf_amd/targets.py against the reference's own run 
 bit, the Matcher on hand-written matrices, the coder's round trip, the sampler's counts and frequencies, and the argument
 validation of the two exports (tests/box_targets_abi_child.py)."""
 import hashlib
-import json
 import math
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -15,6 +13,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_probe  # noqa: E402
 import box_targets_cases as bc  # noqa: E402
 import box_targets_reference as br  # noqa: E402
 
@@ -268,15 +267,7 @@ def test_float_keys_preserve_the_order():
 
 @pytest.fixture(scope="module")
 def abi():
-    from instance_nerf_amd import _lib, build
-    if not os.path.exists(_lib.LIB_PATH):
-        build.build(verbose=False)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "box_targets_abi_child.py")], capture_output=True,
-                       text=True, timeout=600)
-    assert r.returncode == 0, f"the child died (rc {r.returncode}): an export crashed on bad arguments\n{r.stderr[-2000:]}"
-    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-    assert out["alive"] == [0, "reached the end"]
-    return out
+    return abi_probe.run_abi_child("box_targets_abi_child.py")
 
 
 @pytest.mark.parametrize("name", ["inr_box_match_gt_max", "inr_box_match_assign"])

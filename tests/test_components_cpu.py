@@ -1,9 +1,7 @@
 """Connected components of a label volume, CPU side: the composable (plain torch) path of extract.label_components /
 filter_components against the scipy restatement in tests/components_reference.py - exact integers - plus the keep rule,
 floater recovery on the analytic room, and the argument validation of the new exports (child process, no GPU)."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -11,6 +9,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_probe  # noqa: E402
 import components_reference as ref  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -192,15 +191,7 @@ def test_floater_recovery(room, connectivity):
 # ---- ABI -------------------------------------------------------------------------------------------------------------
 @pytest.fixture(scope="module")
 def abi():
-    from instance_nerf_amd import _lib, build
-    if not os.path.exists(_lib.LIB_PATH):
-        build.build(verbose=False)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "components_abi_child.py")], capture_output=True, text=True,
-                       timeout=600, env=dict(os.environ, HIP_VISIBLE_DEVICES=os.environ.get("HIP_VISIBLE_DEVICES", "")))
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-    assert out["alive"] == [0, "reached the end"]
-    return out
+    return abi_probe.run_abi_child("components_abi_child.py", env=abi_probe.NO_GPU)
 
 
 @pytest.mark.parametrize("case,needle", [

@@ -11,7 +11,7 @@ rays whose termination is ambiguous in fp32 left out (at most one of 51, asserte
 Every ray set holds 0, 1, 2, 15 .. 17, 63 .. 65, 127 .. 129, 191 .. 193, 511 and 1024 samples (both sides of every
 64-sample chunk boundary, a third and a sixteenth chunk) three times over, shuffled, ids permuted: 51 rays, a ragged
 last 16-ray group, groups mixing empty and long rays.  Every buffer a kernel writes is a view inside a larger allocation
-with NaN-pattern guard words on both sides (Buf of test_train_kernels.py) and starts out as that NaN pattern wherever
+with NaN-pattern guard words on both sides (Buf of kernel_harness.py) and starts out as that NaN pattern wherever
 the kernel has to write it: a row it skips, or a guard it touches, fails the test.
 
 Seen on an MI355X (each comparison prints its own figure): the forward's weights_sum 5.5e-6 of 6.2e-6 allowed, depth 6.3e-5
@@ -33,7 +33,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import composite_reference as cr  # noqa: E402
 import train_kernels_reference as tk  # noqa: E402
-from test_train_kernels import SENTINEL, Buf, check, stream  # noqa: E402
+from kernel_harness import SENTINEL, Buf, check, finish, nan_out, stream  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 f = np.float32
@@ -139,19 +139,17 @@ def _pad(a, M, K=None):
 def _fresh(shape, dtype=f, written=None):
     """An output buffer: the NaN pattern where the kernel must write (everywhere, or the rows of ``written``), zero -
     the caller's fill - elsewhere."""
-    b = Buf(np.zeros(shape, dtype))
     if written is None:
-        b.fill_nan()
-    else:
-        b.t[torch.from_numpy(written).to(b.t.device)] = float("nan") if dtype == f else -7
+        return nan_out(*np.atleast_1d(shape), dtype=dtype)
+    b = Buf(np.zeros(shape, dtype))
+    b.t[torch.from_numpy(written).to(b.t.device)] = float("nan") if dtype == f else -7
     return b
 
 
-def _sync_and_guards(bufs, what):
-    torch.cuda.synchronize()
-    for name, b in bufs.items():
-        if b is not None:
-            b.check_guards(f"{what} {name}")
+def _finish(ins, out, what):
+    """Guards of inputs and outputs alike -> the outputs' contents, None for an output that was not asked for."""
+    got = finish(dict(ins, **out), what)
+    return {k: got.get(k) for k in out}
 
 
 def _ptr(b):
@@ -170,8 +168,7 @@ def run_forward(lib, c, M, K, weights=True):
                                                _ptr(ins["ex"]), K, out["weights_sum"].ptr, out["depth"].ptr,
                                                out["image"].ptr, _ptr(out["extra_out"]), _ptr(out["weights"]),
                                                _ptr(out["sample_ray"]), stream()), "composite_rays_train_forward")
-    _sync_and_guards(dict(ins, **out), "forward")
-    return {k: None if b is None else b.get() for k, b in out.items()}
+    return _finish(ins, out, "forward")
 
 
 def run_backward(lib, c, M, K, fwd, total=None, field=True, with_g_ws=True):
@@ -194,8 +191,7 @@ def run_backward(lib, c, M, K, fwd, total=None, field=True, with_g_ws=True):
         ins["rgb"].ptr, None, ins["dl"].ptr, ins["rays"].ptr, ins["ws"].ptr, ins["img"].ptr, _ptr(ins["w"]), N, M, T, K,
         _ptr(out["grad_sigmas"]), _ptr(out["grad_rgbs"]), _ptr(out["grad_extra"]), _ptr(ins["total"]), stream()),
         "composite_rays_train_backward")
-    _sync_and_guards(dict(ins, **out), "backward")
-    return {k: None if b is None else b.get() for k, b in out.items()}
+    return _finish(ins, out, "backward")
 
 
 def run_extra_ce(lib, c, K, weights, labels=None, n_classes=0, ignore_index=-1):
@@ -211,8 +207,7 @@ def run_extra_ce(lib, c, K, weights, labels=None, n_classes=0, ignore_index=-1):
                                                _ptr(ins["labels"]), n_classes, ignore_index, _ptr(out.get("dpix")),
                                                _ptr(out.get("part")), _ptr(out.get("loss")), stream()),
           "composite_rays_extra_forward")
-    _sync_and_guards(dict(ins, **out), "extra forward")
-    return {k: b.get() for k, b in out.items()}
+    return _finish(ins, out, "extra forward")
 
 
 @functools.lru_cache(maxsize=None)
@@ -240,8 +235,7 @@ def run_patch(lib, c, M, K, weights=True, hide=None):
                                                _ptr(ins["ex"]), K, out["weights_sum"].ptr, out["depth"].ptr,
                                                out["image"].ptr, _ptr(out["extra_out"]), _ptr(out["weights"]),
                                                out["skippable"].ptr, stream()), "composite_rays_patch_forward")
-    _sync_and_guards(dict(ins, **out), "patch forward")
-    got = {k: None if b is None else b.get() for k, b in out.items()}
+    got = _finish(ins, out, "patch forward")
     got["skippable"] = int(got["skippable"].view(np.int64)[0])
     return got, slots
 
@@ -263,8 +257,7 @@ def run_wavefront(lib, c, n_step, K, T_thresh):
         assert ((after == alive) | (after == -1)).all()
         return after
     calls = cr.wavefront_run(c, n_step, step, K)
-    _sync_and_guards(st, "wavefront")
-    got = {k: None if b is None else b.get() for k, b in st.items()}
+    got = _finish({}, st, "wavefront")
     got["calls"] = calls
     return got
 

@@ -3,10 +3,8 @@ against the numpy restatement (tests/confusion_reference.py) integer for integer
 against torch.argmax on CPU tensors, SegmentationMeter against MIoUMeter with ==, panoptic quality on hand-written
 matrices, the argument validation of the two exports (tests/confusion_abi_child.py) and reduce() on a two-rank gloo
 group.  Everything here is exact: integers, or float64 quotients of the same integers."""
-import json
 import os
 import socket
-import subprocess
 import sys
 
 import numpy as np
@@ -14,6 +12,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_probe  # noqa: E402
 import confusion_reference as cr  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -310,15 +309,7 @@ def test_a_pixel_predicted_outside_the_classes_counts_against_its_truth_only():
 # ---------------------------------------------------------------------------- ABI
 @pytest.fixture(scope="module")
 def abi():
-    from instance_nerf_amd import _lib, build
-    if not os.path.exists(_lib.LIB_PATH):
-        build.build(verbose=False)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "confusion_abi_child.py")], capture_output=True, text=True,
-                       timeout=600)
-    assert r.returncode == 0, f"the child died (rc {r.returncode}): an export crashed on bad arguments\n{r.stderr[-2000:]}"
-    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-    assert out["alive"] == [0, "reached the end"]
-    return out
+    return abi_probe.run_abi_child("confusion_abi_child.py")
 
 
 @pytest.mark.parametrize("name", ["inr_confusion_ids", "inr_confusion_logits"])

@@ -23,7 +23,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import confusion_reference as cr  # noqa: E402
 from test_confusion_cpu import argmax_rows, ids_case, padded, random_views  # noqa: E402
-from test_train_kernels import DEV, Buf, check, stream  # noqa: E402
+from kernel_harness import DEV, Buf, check, stream  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 i32, f32 = np.int32, np.float32

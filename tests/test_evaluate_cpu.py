@@ -1,9 +1,7 @@
 """3-D mask metric (instance_nerf_amd/evaluate.py) on the CPU: the composable path against the reference's own run (the
 golden fixture) and a brute-force count, the label-volume form, files of write_instance_masks_npz, the analytic room, and
 the argument validation of the new exports."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -11,6 +9,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_probe  # noqa: E402
 import evaluate_cases as ec  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -219,15 +218,7 @@ def test_exports_are_registered_and_the_abi_version_is_unchanged():
 
 @pytest.fixture(scope="module")
 def abi():
-    from instance_nerf_amd import _lib, build
-    if not os.path.exists(_lib.LIB_PATH):
-        build.build(verbose=False)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "overlap_abi_child.py")], capture_output=True, text=True,
-                       timeout=600, env=dict(os.environ, HIP_VISIBLE_DEVICES=os.environ.get("HIP_VISIBLE_DEVICES", "")))
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-    assert out["alive"] == [0, "reached the end"]
-    return out
+    return abi_probe.run_abi_child("overlap_abi_child.py", env=abi_probe.NO_GPU)
 
 
 @pytest.mark.parametrize("case,needle", [(f"{name}:{case}", "V must") for name in NEW for case in

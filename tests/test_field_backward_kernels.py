@@ -6,9 +6,7 @@ elementwise.  Sizes come from the device's CU count (one workgroup ... three rou
 density_scale 1 and 0.5, the two device scalars null and given, n_dev null / M - 37 / 0 / above M, rays without
 samples, unsorted sample_ray, the side zero-fill null and with zero_floats % 4 = 0 .. 3 and longer than one grid trip.
 Guards and NaN poisons: tests/field_backward_child.py."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -18,7 +16,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import field_backward_child as L  # noqa: E402
 import field_backward_reference as R  # noqa: E402
-from test_train_kernels import check, cu_count, stream  # noqa: E402
+from kernel_harness import check, cu_count, pack_instance_device, pack_nerf_device, run_result_child, stream  # noqa: E402
 from train_kernels_reference import assert_same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -83,7 +81,7 @@ def test_nerf_head_masks_are_the_forwards(lib, table):
     x, d = C._dev(C.points(table, M, False)), C._dev(C.dirs_for(table, M))
     E = lambda w: torch.zeros(M, w, device="cuda")
     sigma, rgb, enc, h1, so, cin, c1, c2 = torch.zeros(M, device="cuda"), E(3), E(32), E(64), E(16), E(32), E(64), E(64)
-    pf, pb, keep = L.pack_nerf(lib, st.nerf_w)
+    pf, pb, keep = pack_nerf_device(lib, st.nerf_w)
     p = lambda t: t.data_ptr()
     check(lib.inr_nerf_forward_train(p(x), p(d), M, 1.0, p(st.emb), st.desc, pf.ptr, p(sigma), p(rgb), p(enc), p(h1), p(so),
                                      p(cin), p(c1), p(c2), stream()), "forward_train")
@@ -106,7 +104,7 @@ def test_instance_head_masks_are_the_forwards(lib, table, K):
     W = [R._u(rng, (64, 32), 0.35), R._u(rng, (64, 64), 0.25), R._u(rng, (K, 64), 0.25)]
     x = C._dev(C.points(table, M, False))
     logits, enc, h1, h2 = (torch.zeros(M, w, device="cuda") for w in (K, 32, 64, 64))
-    pf, pb, keep = L.pack_instance(lib, W, K)
+    pf, pb, keep = pack_instance_device(lib, W, K)
     p = lambda t: t.data_ptr()
     check(lib.inr_instance_forward_train(p(x), M, 1.0, p(st.emb), st.desc, pf.ptr, K, p(logits), p(enc), p(h1), p(h2),
                                          stream()), "forward_train")
@@ -126,10 +124,7 @@ def test_fp32_library_both_tiers():
     from instance_nerf_amd import build
     assert os.path.exists(build.LIB_FP32), "libinr_hip_fp32.so is built by __graft_entry__.build()"
     child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "field_backward_child.py")
-    r = subprocess.run([sys.executable, child], env=dict(os.environ, INR_LIB_PATH=build.LIB_FP32, FIELD_BACKWARD_BUILD="fp32"),
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
+    res = run_result_child(child, dict(INR_LIB_PATH=build.LIB_FP32, FIELD_BACKWARD_BUILD="fp32"), timeout=600)
     print("fp32 library, worst |got - ref| / cond:", res["ratios"])
     assert res["build"] == "fp32" and {k.split("@")[0] for k in res["ratios"]} == set(R.TOL["fp32"])
     assert not res["failures"], res["failures"][:10]

@@ -6,10 +6,8 @@ directions and inr_nerf_forward_lattice.  Exact tier: bit equality with the floa
 tier: |got - ref| <= TOL * cond elementwise.  Sizes 1 .. 33 around the tile and pair boundaries, 16*61+7, and once each
 for the plain rgb, table and records feed the smallest launch on the hybrid schedule; 0; the device-side sample count;
 the fp16-table identity; dead levels; the fp32 library through a child."""
-import json
 import os
 import re
-import subprocess
 import sys
 
 import numpy as np
@@ -18,7 +16,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import field_forward_child as L  # noqa: E402
 import field_forward_reference as R  # noqa: E402
-from test_train_kernels import stream  # noqa: E402
+from kernel_harness import nan_out, poisoned, run_result_child, stream  # noqa: E402
 from train_kernels_reference import assert_same_bits  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -62,7 +60,7 @@ def test_the_hybrid_size_runs_once_per_feed():
 def test_empty_launches_write_nothing(lib):
     """M == 0 (and an empty lattice): return code 0 with every array null but one poisoned output, which stays poisoned."""
     D = L.dev("levels5")
-    out = L._out(64)
+    out = nan_out(64)
     p, e, d, s = out.ptr, D.emb[0].ptr, D.desc, stream()
     rcs = [lib.inr_nerf_forward(None, None, 0, None, 1.0, e, d, None, 1.0, p, None, None, 0, s),
            lib.inr_nerf_forward_table(None, None, None, 0, 1.0, e, d, None, 1.0, p, None, 0, s),
@@ -78,7 +76,7 @@ def test_empty_launches_write_nothing(lib):
            lib.inr_ray_table_q(None, None, 0, p, s)]
     L._sync()
     assert rcs == [0] * len(rcs), rcs
-    assert L.poisoned(out.get()).all()
+    assert poisoned(out.get()).all()
     out.check_guards("empty launch")
 
 
@@ -97,7 +95,7 @@ def test_device_side_sample_count(lib, entry, n):
 
 def test_records_feed_refuses_a_bound_that_is_no_power_of_two(lib):
     got, _ = L.launch(lib, "levels5", "records", 33, bound=1.5, expect_rc=-1)       # INR_EINVAL
-    assert all(L.poisoned(v).all() for v in got.values())
+    assert all(poisoned(v).all() for v in got.values())
 
 
 @pytest.mark.parametrize("table", ["dense_coarse", "hashed_all", "bench", "all_dense", "levels12", "levels5", "x16"])
@@ -179,10 +177,7 @@ def test_fp32_library_both_tiers():
     from instance_nerf_amd import build
     assert os.path.exists(build.LIB_FP32), "libinr_hip_fp32.so is built by __graft_entry__.build()"
     child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "field_forward_child.py")
-    r = subprocess.run([sys.executable, child], env=dict(os.environ, INR_LIB_PATH=build.LIB_FP32, FIELD_FORWARD_BUILD="fp32"),
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
+    res = run_result_child(child, dict(INR_LIB_PATH=build.LIB_FP32, FIELD_FORWARD_BUILD="fp32"), timeout=600)
     print("fp32 library, worst |got - ref| / cond:", res["ratios"])
     assert res["build"] == "fp32" and set(res["ratios"]) == set(R.TOL["fp32"])
     assert not res["failures"], res["failures"][:10]

@@ -3,9 +3,7 @@ C ABI with poisoned, guarded buffers (tests/instance_lattice_child.py).  Lattice
 voxel, labels (ties to the lowest channel) and max-softmax confidence on both tiers, K = 1 .. 64, lattices around the
 16-voxel run, the >= at the threshold, logits that are all <= 0, the interleaved XCD split once, the exact-fp32 library
 through a child.  Statistics: every output bit-equal to the restatement of the launch's summation order."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -14,6 +12,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import instance_lattice_child as C  # noqa: E402
 import instance_lattice_reference as I  # noqa: E402
+from kernel_harness import run_result_child  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -117,10 +116,7 @@ def test_fp32_library_both_tiers():
     from instance_nerf_amd import build
     assert os.path.exists(build.LIB_FP32), "libinr_hip_fp32.so is built by __graft_entry__.build()"
     child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "instance_lattice_child.py")
-    r = subprocess.run([sys.executable, child], env=dict(os.environ, INR_LIB_PATH=build.LIB_FP32, FIELD_FORWARD_BUILD="fp32"),
-                       capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
+    res = run_result_child(child, dict(INR_LIB_PATH=build.LIB_FP32, FIELD_FORWARD_BUILD="fp32"), timeout=600)
     print("fp32 library, worst |got - ref| as a fraction of its tolerance:", res["ratios"])
     assert res["build"] == "fp32" and set(res["ratios"]) == {"logit", "conf", "conf_exact"}
     assert not res["failures"], res["failures"][:10]

@@ -1,7 +1,6 @@
 """CPU side of the 3-D instance-mask extraction: the npz writer against the reader of the pipeline
 (``masks.load_3d_masks``), the host form of the per-channel statistics, the named limits of the two new C exports
 (in a child process, tests/instance_abi_child.py) and the loader's answer to a library older than its binding."""
-import json
 import os
 import shutil
 import subprocess
@@ -10,6 +9,9 @@ import sys
 import numpy as np
 import pytest
 import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_probe  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 EINVAL = -1
@@ -92,14 +94,8 @@ def test_min_voxels_and_caller_labels(tmp_path):
 
 
 def test_named_limits_of_the_instance_mask_exports():
-    from instance_nerf_amd import _lib, build
-    if not os.path.exists(_lib.LIB_PATH):
-        build.build(verbose=False)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "instance_abi_child.py")], capture_output=True,
-                       text=True, timeout=300, env=dict(os.environ, HIP_VISIBLE_DEVICES=os.environ.get("HIP_VISIBLE_DEVICES", "")))
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-    assert out.pop("alive") == [0, "reached the end"]
+    out = abi_probe.run_abi_child("instance_abi_child.py", env=abi_probe.NO_GPU)
+    del out["alive"]
     needles = {"K_0": "K", "K_65": "K", "confidence_misaligned": "misaligned", "packed_misaligned": "misaligned",
                "sigma_thresh_nan": "NaN", "null_desc": "null", "workspace_too_small": "workspace"}
     assert len(out) == 10

@@ -4,7 +4,6 @@ and threshold rules, ``match_seg_dir`` as the script's drop-in, and the argument
 (child process, no GPU)."""
 import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -12,6 +11,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_probe  # noqa: E402
 import match_cases as mc  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -199,15 +199,7 @@ def test_exports_are_registered():
 
 @pytest.fixture(scope="module")
 def abi():
-    from instance_nerf_amd import _lib, build
-    if not os.path.exists(_lib.LIB_PATH):
-        build.build(verbose=False)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "match_abi_child.py")], capture_output=True, text=True,
-                       timeout=600, env=dict(os.environ, HIP_VISIBLE_DEVICES=os.environ.get("HIP_VISIBLE_DEVICES", "")))
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-    assert out["alive"] == [0, "reached the end"]
-    return out
+    return abi_probe.run_abi_child("match_abi_child.py", env=abi_probe.NO_GPU)
 
 
 @pytest.mark.parametrize("case,needle", [(f"{name}:{case}", needle) for name in NEW[1:] for case, needle in (

@@ -2,15 +2,14 @@
 (tests/mesh_reference.py, the yardstick of the kernels in tests/test_mesh_extract.py) on analytic and random fields, the
 PLY writer / reader, the public surface (``Trainer.save_mesh``), and the argument validation of the three exports."""
 import inspect
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_probe  # noqa: E402
 import mesh_reference as mr  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -216,15 +215,7 @@ def test_extract_mesh_rejects_cpu_models():
 
 @pytest.fixture(scope="module")
 def abi():
-    from instance_nerf_amd import _lib, build
-    if not os.path.exists(_lib.LIB_PATH):
-        build.build(verbose=False)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "mesh_abi_child.py")], capture_output=True, text=True,
-                       timeout=600, env=dict(os.environ, HIP_VISIBLE_DEVICES=os.environ.get("HIP_VISIBLE_DEVICES", "")))
-    assert r.returncode == 0, f"the child died (rc {r.returncode})\n{r.stderr[-2000:]}"
-    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-    assert out["alive"] == [0, "reached the end"]
-    return out
+    return abi_probe.run_abi_child("mesh_abi_child.py", env=abi_probe.NO_GPU)
 
 
 @pytest.mark.parametrize("case,needle", [

@@ -5,7 +5,7 @@ inr_occ_update (full sweep and listed) and inr_mark_untrained_grid.
 Everything is compared bit for bit with the fp32 restatements (the file is built with -ffp-contract=off and these
 kernels use + - * / and comparisons only); the one sum, mean_sum, against the exactly rounded float64 sum within the
 derived n_cells * 2^-52.  Float buffers a kernel writes sit inside a larger allocation between NaN-pattern guard words
-(Buf of test_train_kernels.py); byte outputs are longer than the call's n_bytes and filled with a sentinel byte.
+(Buf of kernel_harness.py); byte outputs are longer than the call's n_bytes and filled with a sentinel byte.
 
 What each seeded fault is caught by is listed with the tests below ("catches: ...")."""
 import ctypes
@@ -19,7 +19,7 @@ import torch
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import occupancy_reference as R  # noqa: E402
 import train_kernels_reference as tk  # noqa: E402
-from test_train_kernels import Buf, check, cu_count, stream  # noqa: E402
+from kernel_harness import Buf, check, cu_count, stream  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"

@@ -22,7 +22,7 @@ import pytest
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import project_masks_reference as R  # noqa: E402
 import train_kernels_reference as tk  # noqa: E402
-from test_train_kernels import Buf, check, stream  # noqa: E402
+from kernel_harness import Buf, check, stream  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 f = np.float32

@@ -2,15 +2,15 @@
 path against the reference's OWN recorded pooler run (tests/golden/reference_calls.npz, recorded by
 tests/golden/make_reference_calls_golden.py from /root/reference/nerf_rcnn/model/poolers.py), with the oracle's
 roi_align_3d as the callable; the argument checks of the two pyramid exports of include/inr.h."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
 import pytest
 import torch
 
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_probe  # noqa: E402
 from instance_nerf_amd.roi_align import LevelMapper, MultiScaleRoIAlign3D, multiscale_roi_align_3d, poolers
 from oracle import consumers, roialign
 
@@ -148,15 +148,7 @@ def test_fused_path_has_no_cpu_fallback(ref):
 
 @pytest.fixture(scope="module")
 def abi():
-    from instance_nerf_amd import _lib, build
-    if not os.path.exists(_lib.LIB_PATH):
-        build.build(verbose=False)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "pyramid_abi_child.py")], capture_output=True, text=True,
-                       timeout=600, env=dict(os.environ, HIP_VISIBLE_DEVICES=os.environ.get("HIP_VISIBLE_DEVICES", "")))
-    assert r.returncode == 0, f"the child died (rc {r.returncode})\n{r.stderr[-2000:]}"
-    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-    assert out["alive"] == [0, "reached the end"]
-    return out
+    return abi_probe.run_abi_child("pyramid_abi_child.py", env=abi_probe.NO_GPU)
 
 
 @pytest.mark.parametrize("name", ["inr_roi_align_3d_pyramid_forward", "inr_roi_align_3d_pyramid_backward"])

@@ -5,9 +5,7 @@ zero fill, ``evaluated``, dropped groups, rows that must never be read, and the 
 owners against NaN-prefilled outputs.  Tolerance tier: |got - ref| <= TOL * cond elementwise, default and -O numerics,
 and the chain inr_nerf_render -> inr_instance_render the renderer runs.  N == 0, M == 0; the fp32 library through a
 child."""
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -17,7 +15,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import field_forward_child as L  # noqa: E402
 import render_child as H  # noqa: E402
 import render_reference as X  # noqa: E402
-from test_train_kernels import cu_count, stream  # noqa: E402
+from kernel_harness import cu_count, nan_out, poisoned, run_result_child, stream  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
@@ -138,14 +136,14 @@ def test_rows_behind_the_termination_point_are_never_read(lib):
 def test_no_rays_writes_nothing(lib):
     """N == 0: INR_OK with every array null but one poisoned output, which stays poisoned."""
     D = L.dev(X.EXACT_TABLE)
-    out = L._out(64)
+    out = nan_out(64)
     p = out.ptr
     rcs = [lib.inr_nerf_render(None, None, None, None, 0, 0, 1.0, D.emb[0].ptr, D.desc, None, 1.0, 1e-4, p, p, p, p, None,
                                0, 0, stream()),
            lib.inr_instance_render(None, None, None, 0, 0, 1.0, D.emb[0].ptr, D.desc, None, 16, p, 0, None, 0, stream())]
     L._sync()
     assert rcs == [0, 0], rcs
-    assert L.poisoned(out.get()).all()
+    assert poisoned(out.get()).all()
     out.check_guards("N == 0")
 
 
@@ -167,10 +165,7 @@ def test_fp32_library_both_tiers():
     from instance_nerf_amd import build
     assert os.path.exists(build.LIB_FP32), "libinr_hip_fp32.so is built by __graft_entry__.build()"
     child = os.path.join(os.path.dirname(os.path.abspath(__file__)), "render_child.py")
-    r = subprocess.run([sys.executable, child], env=dict(os.environ, INR_LIB_PATH=build.LIB_FP32, RENDER_BUILD="fp32"),
-                       capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0, r.stderr[-3000:]
-    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("RESULT ")][-1][7:])
+    res = run_result_child(child, dict(INR_LIB_PATH=build.LIB_FP32, RENDER_BUILD="fp32"), timeout=300)
     print("fp32 library, worst |got - ref| / cond:", res["ratios"])
     assert res["build"] == "fp32" and set(res["ratios"]) == set(X.TOL["fp32"])
     assert not res["failures"], res["failures"][:10]

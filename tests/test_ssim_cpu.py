@@ -14,9 +14,7 @@ One known answer is restated: all-ones against all-zeros gives C1 / (1 + C1) onl
 The eleven binary32 values of the contract sum to 1 - 1.4e-9, so the exact answer is the closed form in S = (sum g)^2
 below; it is asserted to float64 rounding, and its distance from C1 / (1 + C1) is bounded from |S - 1|.
 """
-import json
 import os
-import subprocess
 import sys
 
 import numpy as np
@@ -24,6 +22,7 @@ import pytest
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import abi_probe  # noqa: E402
 import ssim_reference as sr  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -235,15 +234,7 @@ def test_ssim_meter_data_range():
 # ---------------------------------------------------------------------------- the C ABI's targeted cases
 @pytest.fixture(scope="module")
 def abi():
-    from instance_nerf_amd import _lib, build
-    if not os.path.exists(_lib.LIB_PATH):
-        build.build(verbose=False)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tests", "ssim_abi_child.py")], capture_output=True, text=True,
-                       timeout=600, env=dict(os.environ, HIP_VISIBLE_DEVICES=os.environ.get("HIP_VISIBLE_DEVICES", "")))
-    assert r.returncode == 0, r.stderr[-2000:]
-    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
-    assert out["alive"] == [0, "reached the end"]
-    return out
+    return abi_probe.run_abi_child("ssim_abi_child.py", env=abi_probe.NO_GPU)
 
 
 @pytest.mark.parametrize("case,needle", [

@@ -26,7 +26,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import ssim_reference as sr  # noqa: E402
-from test_train_kernels import DEV, Buf, check, stream  # noqa: E402
+from kernel_harness import DEV, Buf, check, nan_out, stream  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 f32, f64 = np.float32, np.float64
@@ -54,19 +54,13 @@ def case(kind, B, H, W, C, scale=1.0, L=1.0):
     return x, y, sr.tolerance(x, y, L)
 
 
-def nan_buf(shape):
-    b = Buf(np.zeros(shape, f32))
-    b.fill_nan()
-    return b
-
-
 def run(lib, x, y, L=1.0, want_map=True, want_sse=True):
     """One inr_ssim_forward through guarded, NaN-poisoned buffers -> (ssim [B], sse [B] or None, map or None)."""
     B, H, W, C = x.shape
     need = lib.inr_ssim_workspace_bytes(B, H, W, C)
     assert need == B * (-(-(H - 10) // TH)) * (-(-(W - 10) // TW)) * 16
     X, Y, R = Buf(x), Buf(y), Buf(np.array([L], f32))
-    S, E, M, WS = nan_buf((B,)), nan_buf((B,)), nan_buf((B, H - 10, W - 10, C)), nan_buf((need // 4,))
+    S, E, M, WS = nan_out(B), nan_out(B), nan_out(B, H - 10, W - 10, C), nan_out(need // 4)
     assert WS.ptr % 8 == 0
     check(lib.inr_ssim_forward(X.ptr, Y.ptr, B, H, W, C, window().ctypes.data, R.ptr, S.ptr, E.ptr if want_sse else None,
                                M.ptr if want_map else None, WS.ptr, need, stream()), "ssim_forward")

@@ -18,71 +18,19 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import train_kernels_reference as ref  # noqa: E402
+from kernel_harness import DEV, Buf, check, cu_count, stream  # noqa: E402
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 f = np.float32
-GUARD = 64
-SENTINEL = 0x7FC0BEEF                  # a quiet NaN as fp32: a kernel that READS a guard word poisons its result too
 HYPER = dict(lr=1e-2, b1=0.9, b2=0.99, eps=1e-15)
 ADAM_GRID = 4096 * 256                 # k_adam / k_adam_multi: at most 256*16 workgroups of 256 lanes, one float4 each
 BIG = 4 * ADAM_GRID + 4 * 300 + 3      # 4 195 507 floats: 300 float4s on the second grid-stride trip and a 3-float tail
-_TORCH = {np.dtype(np.float32): torch.float32, np.dtype(np.int32): torch.int32, np.dtype(np.uint8): torch.uint8}
 
 
 @pytest.fixture(scope="module")
 def lib():
     from instance_nerf_amd import _lib
     return _lib.load()
-
-
-def check(rc, what=""):
-    from instance_nerf_amd import _lib
-    _lib.check(rc, what)
-
-
-def stream():
-    from instance_nerf_amd import _lib
-    return _lib.stream_ptr()
-
-
-def cu_count(lib):
-    """The CU count the library's launch arithmetic uses (hipDeviceAttributeMultiprocessorCount)."""
-    props = (ctypes.c_int64 * 8)()
-    check(lib.inr_device_info(0, props), "device_info")
-    assert props[0] == torch.cuda.get_device_properties(0).multi_processor_count > 0
-    return int(props[0])
-
-
-class Buf:
-    """``data`` (float32 / int32, or uint8 with a byte count divisible by 4) inside a larger int32 allocation:
-    GUARD sentinel words, ``offset`` more words (1 = a base pointer that is 4- but not 16-byte aligned), the data,
-    GUARD sentinel words."""
-
-    def __init__(self, data, offset=0):
-        data = np.ascontiguousarray(data)
-        self.shape, self.dtype = data.shape, data.dtype
-        words = data.reshape(-1).view(np.int32)
-        self.start, self.words = GUARD + offset, len(words)
-        self.whole = torch.full((self.start + self.words + GUARD,), SENTINEL, dtype=torch.int32, device=DEV)
-        assert self.whole.data_ptr() % 256 == 0
-        self.raw = self.whole[self.start:self.start + self.words]
-        self.raw.copy_(torch.from_numpy(words))
-        self.t = self.raw.view(_TORCH[self.dtype]).view(self.shape)
-
-    @property
-    def ptr(self):
-        return self.raw.data_ptr() if self.words else None
-
-    def get(self):
-        return self.raw.cpu().numpy().view(self.dtype).reshape(self.shape)
-
-    def fill_nan(self):
-        self.raw.fill_(SENTINEL)
-
-    def check_guards(self, what=""):
-        head, tail = self.whole[:self.start], self.whole[self.start + self.words:]
-        assert bool((head == SENTINEL).all()) and bool((tail == SENTINEL).all()), f"{what}: a guard word was written"
 
 
 def same(buf, want, what):
