@@ -43,7 +43,7 @@ extern "C" {
  * 13: inr_components_workspace_bytes, inr_components_label, inr_components_filter.
  * (inr_ssim_workspace_bytes and inr_ssim_forward were ADDED under 13: no prototype changed, nothing was removed; a
  * library built before them is named by the binding's loader, symbol by symbol.  inr_confusion_ids and
- * inr_confusion_logits likewise, and inr_box_match_gt_max and inr_box_match_assign.) */
+ * inr_confusion_logits likewise, inr_box_match_gt_max and inr_box_match_assign, and the four inr_fcos_* exports.) */
 #define INR_ABI_VERSION 13
 #define INR_MAX_LEVELS 16
 
@@ -1162,6 +1162,95 @@ int inr_box_match_assign(const float* gt /*[G,6]*/, const int32_t* gt_labels /*[
                          const uint32_t* gt_max_keys /*[G]*/, float high, float low, int32_t allow_low_quality,
                          int32_t* matched /*[A]*/, int32_t* labels /*[A] nullable*/, float* best_iou /*[A] nullable*/,
                          float* matched_boxes /*[A,6] nullable*/, float* targets /*[A,6] nullable*/, inr_stream_t s);
+
+/* ---- FCOS training targets and losses (csrc/fcos.hip) ---------------------------------------------------------------
+ * What every training step of the reference's FCOS proposal head starts and ends with (nerf_rcnn/model/fcos/loss.py:
+ * prepare_targets, compute_centerness_targets, IOULoss, __call__): one ground-truth box per location of the pyramid, and
+ * the three losses with their gradients, without a [P, G] tensor, a permuted copy of the predictions or a read-back.
+ * Axis-aligned boxes only.  Additive: no version bump.
+ *
+ * Pyramid: HOST arrays as in inr_roi_align_3d_pyramid_forward, travelling in the kernel arguments: level_dims int32
+ * [n_levels*3] = (W, L, H) per level, level_strides int32 [n_levels], level_ranges fp32 [n_levels*2] = (lo_l, hi_l), the
+ * sizes of interest.  P_l = W*L*H, 1 <= n_levels <= INR_FCOS_MAX_LEVELS; B scenes.  Every per-location array is
+ * LEVEL-FIRST, the layout of the reference's lists: level l starts at B * (P_0 + ... + P_{l-1}), scene b of it at
+ * b * P_l more, location p = (ix * L + iy) * H + iz.
+ * Ground truth: gt fp32 [sum G_b, 6], rows (x1, y1, z1, x2, y2, z2), and gt_offsets int32 [B+1] on the DEVICE; scene b
+ * owns rows gt_offsets[b] .. gt_offsets[b+1]-1.  max_gt >= every G_b sizes the LDS (52 B per box); the kernel looks at
+ * no more than max_gt boxes of a scene.  0 <= max_gt <= INR_FCOS_MAX_GT.
+ *
+ * Target rule (all fp32, one operation at a time, no fused multiply-add, IEEE division and square root):
+ *  1. location p of level l has the coordinate i * stride + stride / 2 (integer division) per axis;
+ *  2. reg[g] = (x - x1, y - y1, z - z1, x2 - x, y2 - y, z2 - z);
+ *  3. inside[g]: radius > 0: s = (float)((double)stride * radius), c = (lo + hi) / 2 per axis, rlo = c - s > lo ? c - s : lo,
+ *     rhi = c + s > hi ? hi : c + s, and the minimum of the six distances to (rlo, rhi) is > 0; radius == 0: min(reg[g]) > 0;
+ *  4. cared[g]: max(reg[g]) >= lo_l and max(reg[g]) <= hi_l (a NaN distance fails both tests);
+ *  5. area[g] = inside and cared ? ((x2-x1)*(y2-y1))*(z2-z1) : 1e8f; matched = the arg-min over g, the lowest index among
+ *     equals, a NaN counts as the minimum and the first NaN wins (torch.min on CPU tensors); label = area[matched] != 1e8f
+ *     ? 1 : 0; reg_target = reg[matched] - ALSO where the label is 0, as the reference has it -, divided by (float)stride
+ *     when norm_reg_targets != 0;
+ *  6. centerness = sqrtf((min(r0,r3)/max(r0,r3)) * (min(r1,r4)/max(r1,r4)) * (min(r2,r5)/max(r2,r5))) of reg_target where
+ *     the label is 1 (min and max keep a NaN), 0 elsewhere;
+ *  7. valid = x < w_ori and y < l_ori and z < h_ori with ori_sizes fp32 [B, 3] (valid needs ori_sizes).
+ *  A scene without boxes gives label 0, reg_target 0, centerness 0, matched 0.
+ * inr_fcos_targets: ONE launch for all scenes and levels.  One lane per location; a workgroup of INR_FCOS_BLOCK lanes owns
+ *   INR_FCOS_LOCATIONS_PER_WG consecutive locations of one (level, scene) and stages that scene's boxes, volumes and
+ *   sample regions in LDS once.  Outputs labels fp32 [T], reg_targets fp32 [T, 6] and, each nullable, centerness fp32 [T],
+ *   matched int32 [T], valid uint8 [T], with T = B * sum P_l.
+ *
+ * Losses.  Predictions are the head's own tensors, read in place: per level cls [B,1,W,L,H], reg [B,6,W,L,H]
+ * (channel-planar), ctr [B,1,W,L,H], as HOST arrays of n_levels device pointers.  Per location with valid != 0 (all,
+ * when valid is null), t = label:
+ *   focal  = torchvision's sigmoid_focal_loss(x, t, alpha 0.25, gamma 2): p = sigmoid(x), ce = max(x,0) - x t +
+ *            log1p(exp(-|x|)), p_t = p t + (1-p)(1-t), focal = (alpha t + (1-alpha)(1-t)) * (ce * (1-p_t)^2);
+ *   and where t > 0, with c = the centerness of reg_target (rule 6; recomputed, not read):
+ *   regterm = IOULoss(pred, reg_target) * c (loss.py:85-132 in that operation order; iou_loss_type INR_FCOS_LOSS_IOU
+ *            -log(iou), _LINEAR_IOU 1 - iou, _GIOU 1 - giou);
+ *   bce    = max(y,0) - y c + log1p(exp(-|y|)) of the centerness logit y.
+ *   The reference sums the IoU losses unweighted when the weights do not sum above 0; positives of rule 5 have all six
+ *   distances above 0, so that branch is not followed.
+ * inr_fcos_loss_forward: terms in fp32, five sums in FLOAT64 per workgroup into `workspace`
+ *   (inr_fcos_loss_workspace_bytes(T) bytes, 8-byte aligned; a negative return for a bad T), a second small launch adds
+ *   the partial sums in a fixed order: two calls give the same bits.  sums double [5] = (focal, regterm, bce, n_pos,
+ *   sum of c) - the two normalisers last, adjacent -; losses fp32 [3] = (focal / max(n_pos, 1), regterm / sum c,
+ *   bce / max(n_pos, 1)), the last two 0 when n_pos == 0.  cls_terms, reg_terms, ctr_terms fp32 [T], each nullable: the
+ *   per-location terms, 0 where a term does not apply.
+ * inr_fcos_loss_backward: recomputes each location's derivative and scales it: d_cls = grad_losses[0] / max(norms[0], 1)
+ *   * d focal / dx; d_reg = grad_losses[1] / norms[1] * c * d IOULoss / d pred; d_ctr = grad_losses[2] / max(norms[0], 1)
+ *   * (sigmoid(y) - c).  norms double [2] = (n_pos, sum c) - sums + 3, or their all-reduced average - and grad_losses
+ *   fp32 [3] are read from DEVICE memory.  d_cls, d_reg (channel-planar), d_ctr: HOST arrays of device pointers in the
+ *   predictions' layouts, every element written (0 where valid == 0; d_reg and d_ctr 0 where the label is 0).  Inside
+ *   min / max, pred == target sends half the gradient to each side (torch's rule for minimum / maximum).
+ * Limits, checked before any launch (INR_EINVAL with a message): n_levels in 1..INR_FCOS_MAX_LEVELS, B >= 0, every
+ * extent and stride >= 1 with extent * stride < 2^24, 6 * T < 2^31, max_gt in 0..INR_FCOS_MAX_GT, radius >= 0, a known
+ * iou_loss_type, required pointers not null, fp32 / int32 arrays 4-byte and double arrays 8-byte aligned, the workspace
+ * large enough.  T == 0 (B == 0) is a valid no-op returning 0 after these checks; no device pointer is looked at. */
+#define INR_FCOS_MAX_LEVELS 8
+#define INR_FCOS_MAX_GT 1024
+#define INR_FCOS_BLOCK 256
+#define INR_FCOS_LOCATIONS_PER_WG 256
+#define INR_FCOS_LOSS_LOCATIONS_PER_WG 1024
+#define INR_FCOS_LOSS_IOU 0
+#define INR_FCOS_LOSS_LINEAR_IOU 1
+#define INR_FCOS_LOSS_GIOU 2
+int inr_fcos_targets(const int32_t* level_dims /*host*/, const int32_t* level_strides /*host*/,
+                     const float* level_ranges /*host*/, int32_t n_levels, int32_t B, const float* gt /*[sum G,6]*/,
+                     const int32_t* gt_offsets /*[B+1]*/, int32_t max_gt, const float* ori_sizes /*[B,3] nullable*/,
+                     float radius, int32_t norm_reg_targets, float* labels /*[T]*/, float* reg_targets /*[T,6]*/,
+                     float* centerness /*[T] nullable*/, int32_t* matched /*[T] nullable*/, uint8_t* valid /*[T] nullable*/,
+                     inr_stream_t s);
+int64_t inr_fcos_loss_workspace_bytes(int64_t T);
+int inr_fcos_loss_forward(const float* const* cls_ptrs /*host*/, const float* const* reg_ptrs /*host*/,
+                          const float* const* ctr_ptrs /*host*/, const int32_t* level_dims /*host*/, int32_t n_levels,
+                          int32_t B, const float* labels /*[T]*/, const float* reg_targets /*[T,6]*/,
+                          const uint8_t* valid /*[T] nullable*/, int32_t iou_loss_type, double* sums /*[5]*/,
+                          float* losses /*[3]*/, float* cls_terms /*[T] nullable*/, float* reg_terms /*[T] nullable*/,
+                          float* ctr_terms /*[T] nullable*/, void* workspace, int64_t workspace_bytes, inr_stream_t s);
+int inr_fcos_loss_backward(const float* const* cls_ptrs /*host*/, const float* const* reg_ptrs /*host*/,
+                           const float* const* ctr_ptrs /*host*/, const int32_t* level_dims /*host*/, int32_t n_levels,
+                           int32_t B, const float* labels /*[T]*/, const float* reg_targets /*[T,6]*/,
+                           const uint8_t* valid /*[T] nullable*/, int32_t iou_loss_type, const double* norms /*[2]*/,
+                           const float* grad_losses /*[3]*/, float* const* d_cls_ptrs /*host*/,
+                           float* const* d_reg_ptrs /*host*/, float* const* d_ctr_ptrs /*host*/, inr_stream_t s);
 
 #ifdef __cplusplus
 }

@@ -24,6 +24,9 @@ SSIM_TAPS, SSIM_TILE_W, SSIM_TILE_H = 11, 64, 16    # include/inr.h INR_SSIM_TAP
 CONFUSION_MAX_K, CONFUSION_BLOCK, CONFUSION_PIXELS_PER_WG = 64, 256, 1024
 # include/inr.h INR_BOX_MATCH_MAX_GT, INR_BOX_MATCH_BLOCK, INR_BOX_MATCH_BOXES_PER_WG
 BOX_MATCH_MAX_GT, BOX_MATCH_BLOCK, BOX_MATCH_BOXES_PER_WG = 1024, 256, 1024
+# include/inr.h INR_FCOS_MAX_LEVELS, INR_FCOS_MAX_GT, INR_FCOS_BLOCK, INR_FCOS_LOCATIONS_PER_WG, INR_FCOS_LOSS_LOCATIONS_PER_WG
+FCOS_MAX_LEVELS, FCOS_MAX_GT, FCOS_BLOCK, FCOS_LOCATIONS_PER_WG, FCOS_LOSS_LOCATIONS_PER_WG = 8, 1024, 256, 256, 1024
+FCOS_LOSS_IOU, FCOS_LOSS_LINEAR_IOU, FCOS_LOSS_GIOU = 0, 1, 2      # include/inr.h INR_FCOS_LOSS_*
 
 
 class GridDesc(Structure):
@@ -185,6 +188,10 @@ _SIGS = {
     "inr_confusion_logits": (c_int32, [P, P, c_int64, c_int64, c_int32, c_int64, P, P, P]),
     "inr_box_match_gt_max": (c_int32, [P, c_int32, P, P, c_int64, P, P]),
     "inr_box_match_assign": (c_int32, [P, P, c_int32, P, P, c_int64, P, c_float, c_float, c_int32, P, P, P, P, P, P]),
+    "inr_fcos_targets": (c_int32, [P, P, P, c_int32, c_int32, P, P, c_int32, P, c_float, c_int32, P, P, P, P, P, P]),
+    "inr_fcos_loss_workspace_bytes": (c_int64, [c_int64]),
+    "inr_fcos_loss_forward": (c_int32, [P, P, P, P, c_int32, c_int32, P, P, P, c_int32, P, P, P, P, P, P, c_int64, P]),
+    "inr_fcos_loss_backward": (c_int32, [P, P, P, P, c_int32, c_int32, P, P, P, c_int32, P, P, P, P, P, P]),
 }
 EXPORTS = tuple(_SIGS)
 
@@ -213,7 +220,7 @@ def load():
                            "INR_ABI_VERSION): rebuild with `python -m instance_nerf_amd.build --force`")
     for name, (res, args) in _SIGS.items():
         fn = getattr(lib, name, None)
-        if fn is None:                  # exports added without a version bump (inr_ssim_*, inr_confusion_*, inr_box_match_*): a library built before them
+        if fn is None:                  # exports added without a version bump (inr_ssim_*, inr_confusion_*, inr_box_match_*, inr_fcos_*): a library built before them
             raise RuntimeError(f"{LIB_PATH} does not export {name} (include/inr.h): rebuild with "
                                "`python -m instance_nerf_amd.build --force`")
         fn.restype = res

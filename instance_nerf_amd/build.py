@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(CSRC, "libinr_hip.so")
 SOURCES = ["raymarch.hip", "encoders.hip", "field_fused.hip", "roialign.hip", "mesh.hip", "components.hip", "match.hip",
-           "overlap.hip", "detect.hip", "background.hip", "ssim.hip", "confusion.hip", "assign.hip"]
+           "overlap.hip", "detect.hip", "background.hip", "ssim.hip", "confusion.hip", "assign.hip", "fcos.hip"]
 HEADERS = ["common.h", "grid_common.h", "sample_pos.h", "box_iou.h", os.path.join("..", "..", "include", "inr.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
          "-munsafe-fp-atomics", "-Wall", "-Wno-unused-function"]
@@ -28,6 +28,7 @@ KERNEL_FILES = {
     "ssim": ["ssim.hip", "common.h"],                                 # k_ssim_tiles, k_ssim_finish
     "confusion": ["confusion.hip", "common.h"],                       # k_confusion_ids, k_confusion_logits
     "assign": ["assign.hip", "box_iou.h", "common.h"],                # k_box_match_gt_max, k_box_match_assign
+    "fcos": ["fcos.hip"],                                             # k_fcos_targets, k_fcos_loss_forward / _finish / _backward
 }
 
 
