@@ -537,7 +537,12 @@ int inr_nerf_forward_table(const float* x01, const int32_t* ray_ids, const float
  * Launches with numerics 0 on a 16-level table whose levels 8..15 are all hashed run behind the pair front end
  * (k_nerf_fwd_pair: a wave encodes two consecutive tiles in one gather pass, two lanes per sample; same bits).
  * INR_FIELD_PAIR=0 in the process environment, read at every launch, selects the one-tile kernel for them too - a
- * switch for A/B measurements and tests, no export and no ABI change.                                               */
+ * switch for A/B measurements and tests, no export and no ABI change.
+ * Where levels 0..3 of that table are all dense, the pair front end fetches their x-neighbour rows - adjacent on a dense
+ * level - in one 16-byte load per yz corner (same bits).  INR_FIELD_COARSE=0 in the environment, read at every launch,
+ * selects the 8-byte gathers for those launches too.  The debug counters below - plain data, not part of the function
+ * ABI, not thread-safe - count the pair launches: [1] with the 16-byte loads, [0] without.                            */
+extern int64_t inr_debug_field_coarse_launches[2];
 #define INR_RAY_TABLE_FLOATS 24
 int inr_ray_table_q(const float* rays_o /*[N,3]*/, const float* rays_d /*[N,3]*/, int64_t N, float* out, inr_stream_t s);
 int inr_nerf_forward_table_records(const float* t, const int32_t* ray_ids, const float* ray_table_q, int64_t M,

@@ -1151,6 +1151,8 @@ __global__ void __launch_bounds__(kFieldThreads, kFieldMinWaves) k_nerf_fwd(cons
 // on any CU and the frame loop LOSES 1 % although the kernel itself is 14 % faster; this form needs 196 and leaves the
 // marchers the wave per SIMD they had.  Waits (INR_PAIR_WAIT_*, as in issue_gathers_impl) swept again for this form:
 // 16 / 8 here; 8 / 4, 32 / 16, 16 / 4 and none are 0.4-1.2 % slower (profiles/r09_pair_gather_bench.md).
+// Where levels 0..3 are all dense (the bench table: 0..4) the coarse slots 0 and 1 take issue_coarse_pair_dense: 24
+// coarse gather instructions instead of 32, 56 per pair instead of 64; the waits above were not swept again for it.
 #ifndef INR_PAIR_WAIT_COARSE
 #define INR_PAIR_WAIT_COARSE 16
 #endif
@@ -1190,6 +1192,60 @@ __device__ __forceinline__ void issue_coarse_pair(const LevelRec* __restrict__ m
     for (int k = 0; k < 8; ++k) g.c[c][k] = gather_at(rsrc, off[k]);
     keep_offsets(off[0], off[1], off[2], off[3]);
     keep_offsets(off[4], off[5], off[6], off[7]);
+  }
+}
+
+// Dense x-pairs for the coarse slots 0 and 1 (levels {0 | 2} and {1 | 3}); the host takes it when all four are dense.
+// On a dense level row(cx + 1) = row(cx) + 1 and nothing wraps (mask all ones), so the two x-neighbour rows of a yz
+// corner come in ONE 16-byte load at 8-byte alignment: four offsets and four instructions per level instead of eight,
+// row = cx + hy + hz without the dense/hashed lane masks of index_terms.  The halves are corners k and k + 1 of
+// blend_coarse_pair.  Slots 2 and 3 (levels 4..7) mix dense and hashed lanes and stay as they are.  Same rows, same
+// weights, same corner order: the same bits.  Measured (tools/micro/coarse_row_bench.hip, profiles/r12_coarse_rows_*.md):
+// the vector memory path prices a 16-byte lane-load like an 8-byte one (18.9 against 35.5 clk per wave and row pair);
+// 60 VALU fewer per pair; field launch 4.05 -> 3.94 ms inside the view loop, frame loop +2.5 %.
+// Built beside it, measured and left out: level 0 read from a copy in the launch's idle LDS by the s = 0 lanes of slot 0.
+// A gather instruction with half its lanes active costs what it costs with all of them (33.0 against 35.5 clk), so the
+// s = 1 lanes' level 2 keeps slot 0's instructions in the texture path at full price: frame loop -0.4 % alone, and +1.8 %
+// together with the x-pairs, which alone give +2.5 %.
+typedef unsigned int u32x4 __attribute__((__vector_size__(4 * sizeof(unsigned int))));
+__device__ __forceinline__ void issue_coarse_pair_dense(const LevelRec* __restrict__ my_recs, __amdgpu_buffer_rsrc_t rsrc,
+                                                        float x0, float x1, float x2, GatheredPair& g) {
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const LevelRec* rec = my_recs + (c >> 1) * 8 + (c & 1);
+    const uint4 ra = rec->a;
+    const float s = __uint_as_float(ra.x);
+    const uint32_t base = ra.y, pa = ra.z, pb = ra.w;
+    const float px = x0 * s + 0.5f, py = x1 * s + 0.5f, pz = x2 * s + 0.5f;   // mul, add: not fused
+    g.cfx[c] = __builtin_amdgcn_fractf(px); g.cfy[c] = __builtin_amdgcn_fractf(py); g.cfz[c] = __builtin_amdgcn_fractf(pz);
+    const uint32_t cx = (uint32_t)px, cy = (uint32_t)py, cz = (uint32_t)pz;
+    const uint32_t hy0 = cy * pa, hy1 = hy0 + pa;
+    const uint32_t hz0 = cz * pb, hz1 = hz0 + pb;
+    if (c < 2) {
+      uint32_t off[4];           // byte offsets of the row pairs (y0z0, y1z0, y0z1, y1z1)
+      off[0] = base + (cx + (hy0 + hz0)) * 8u;
+      off[1] = base + (cx + (hy1 + hz0)) * 8u;
+      off[2] = base + (cx + (hy0 + hz1)) * 8u;
+      off[3] = base + (cx + (hy1 + hz1)) * 8u;
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)off[k], 0, 0);
+        g.c[c][2 * k] = u32x2{v[0], v[1]};
+        g.c[c][2 * k + 1] = u32x2{v[2], v[3]};
+      }
+      keep_offsets(off[0], off[1], off[2], off[3]);
+    } else {
+      const uint4 rb = rec->b;
+      const uint32_t mask = rb.x;
+      const IndexTerms t = index_terms(hy0, hy1, hz0, hz1, rb.z, rb.w);
+      uint32_t off[8];
+#pragma unroll
+      for (int k = 0; k < 8; ++k) off[k] = base + t.row(cx + (k & 1), k >> 1, mask) * 8u;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) g.c[c][k] = gather_at(rsrc, off[k]);
+      keep_offsets(off[0], off[1], off[2], off[3]);
+      keep_offsets(off[4], off[5], off[6], off[7]);
+    }
   }
 }
 
@@ -1312,6 +1368,8 @@ __device__ __forceinline__ void pair_mlp(const float4* __restrict__ wl, int lane
 
 // The records feed of k_nerf_fwd<true, true, 0, false, false, false, true> behind the pair front end; same arguments
 // where it has them.  The host takes it only for a 16-level fp32 table whose levels 8..15 are all hashed.
+// kDenseX: levels 0..3 are all dense (the host's dense_x_pairs_qualify decides) - issue_coarse_pair_dense.
+template <bool kDenseX = false>
 __global__ void __launch_bounds__(kFieldThreads, kFieldMinWaves) k_nerf_fwd_pair(
     const float* __restrict__ x, int64_t M, float bound, const float2* __restrict__ emb, uint32_t emb_bytes, GridDesc G,
     const float4* __restrict__ packed, float density_scale, float* __restrict__ sigma, float* __restrict__ rgb,
@@ -1357,7 +1415,9 @@ __global__ void __launch_bounds__(kFieldThreads, kFieldMinWaves) k_nerf_fwd_pair
       asm volatile("" : "+v"(rec_off));    // opaque per pair: keeps the records in LDS, not hoisted into VGPRs
       // 32 coarse + 16 fine gathers out, the coarse blend under the fine loads, then the other 16: at most 48 rows
       // (96 registers) are held at once, which leaves the marchers of the next view their registers on the CU
-      issue_coarse_pair(reinterpret_cast<const LevelRec*>(reinterpret_cast<const char*>(recs) + rec_off), rsrc, x0, x1, x2, g);
+      const LevelRec* my_recs = reinterpret_cast<const LevelRec*>(reinterpret_cast<const char*>(recs) + rec_off);
+      if constexpr (kDenseX) issue_coarse_pair_dense(my_recs, rsrc, x0, x1, x2, g);
+      else issue_coarse_pair(my_recs, rsrc, x0, x1, x2, g);
       issue_fine_pair<0>(G, rsrc, side, x0, x1, x2, g);
       __builtin_amdgcn_sched_barrier(0);
       blend_coarse_pair(g, enc_a, enc_b);
@@ -3192,6 +3252,18 @@ static bool pair_front_end_qualifies(const inr_grid_desc* desc, int32_t numerics
   return !(off && off[0] == '0' && off[1] == 0);
 }
 
+// k_nerf_fwd_pair<true> (dense x-pairs: one 16-byte load per x-neighbour row pair of levels 0..3) where those four levels
+// are all dense; any other table takes k_nerf_fwd_pair<false>, the kernel of before.  INR_FIELD_COARSE=0 in the
+// environment - read at every launch, like INR_FIELD_PAIR - selects the latter for every table (A/B runs and tests).
+// inr_debug_field_coarse_launches[v] (include/inr.h) counts the pair launches that took <v>: how a test sees the gate.
+extern "C" int64_t inr_debug_field_coarse_launches[2];
+static bool dense_x_pairs_qualify(const inr_grid_desc* desc) {
+  for (int l = 0; l < 4; ++l)
+    if (desc->hashed[l]) return false;
+  const char* off = getenv("INR_FIELD_COARSE");
+  return !(off && off[0] == '0' && off[1] == 0);
+}
+
 template <bool kRec>
 static int forward_table_launch(const char* what, const float* x, const int32_t* ray_ids, const float* table, int64_t M,
                                 float bound, const void* embeddings, const inr_grid_desc* desc, const float* packed,
@@ -3205,8 +3277,12 @@ static int forward_table_launch(const char* what, const float* x, const int32_t*
   HybridSchedule hybrid;         // frames (four rounds of eight 1024-tile chunks and more)
   if (!hybrid.begin(st, n_tiles)) return INR_ELAUNCH;
   if (kRec && pair_front_end_qualifies(desc, numerics)) {
-    launch_field(k_nerf_fwd_pair, lds, (n_tiles + 1) / 2, st, x, M, bound, t.emb, t.bytes, t.G, f4(packed), density_scale,
-                 sigma, rgb, ray_ids, f4(table), hybrid.cursors());
+    const bool dense = dense_x_pairs_qualify(desc);
+    with_flag(dense, [&](auto dx) {
+      launch_field(k_nerf_fwd_pair<decltype(dx)::value>, lds, (n_tiles + 1) / 2, st, x, M, bound, t.emb, t.bytes, t.G,
+                   f4(packed), density_scale, sigma, rgb, ray_ids, f4(table), hybrid.cursors());
+    });
+    ++inr_debug_field_coarse_launches[dense ? 1 : 0];
     hybrid.finish(st);
     return check_launch(what + 4);
   }
@@ -3242,6 +3318,8 @@ __global__ void __launch_bounds__(256) k_ray_table_q(const float* __restrict__ o
 using namespace inr;
 
 extern "C" {
+
+int64_t inr_debug_field_coarse_launches[2] = {0, 0};
 
 int64_t inr_nerf_packed_floats(void) { return kNerfFloats; }
 

@@ -47,6 +47,15 @@ def level_table(num_levels=16, level_dim=2, base_resolution=16, log2_hashmap_siz
                 total_rows=int(offsets[-1]))
 
 
+def dense_x_pairs(table, switch=None):
+    """What the library's host gate (dense_x_pairs_qualify in csrc/field_fused.hip) decides for a frame launch behind the
+    pair front end, restated: True where levels 0..3 are all dense - their x-neighbour rows then come in one 16-byte
+    load - unless ``switch`` (INR_FIELD_COARSE) is "0".  The library counts its own choice in
+    ``inr_debug_field_coarse_launches``; tests/test_coarse_rows.py holds the two against each other."""
+    hashed = [int(v) for v in table["hashed"]]
+    return len(hashed) >= 4 and not any(hashed[:4]) and str(switch) != "0"
+
+
 class _GridEncode(torch.autograd.Function):
     @staticmethod
     def forward(ctx, inputs, embeddings, desc, bound, out_dim):
