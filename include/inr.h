@@ -225,7 +225,11 @@ int inr_occ_sample_cells(const float* grid /*[n_cells] Morton order*/, int64_t n
  * independent of the grid), which of each ray's first sample_cap candidates were emitted; the write pass
  * regenerates the sequence and emits at the set bits instead of walking the occupancy grid again (rays that
  * need more candidates are re-marched); pass the SAME workspace and sample_cap to the write call.  Results
- * are identical.                                                                                        */
+ * are identical.
+ * Preconditions (every march entry point: _count, _write, the patch writers, inr_march_rays): each ray's direction is a
+ * nonzero vector, and far is finite wherever near < far - what inr_near_far_from_aabb produces (a miss is
+ * near = far = FLT_MAX and is never marched).  They are not checked: a zero direction, or an unbounded far in empty
+ * space, gives a walk that does not end, because t stops growing once the step falls below half an ulp of t.    */
 /* 1 when inr_march_rays_train_write zero-fills the rows of xyzs / dirs / deltas that no ray owns by itself (the staged
  * wave-per-ray marcher does; the caller may then pass uninitialised buffers), 0 when the caller must zero them first. */
 int inr_march_write_fills_unowned_rows(int64_t N, int32_t sample_cap, int32_t max_steps);

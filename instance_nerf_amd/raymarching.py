@@ -220,6 +220,10 @@ def march_rays_train(rays_o, rays_d, bound, density_bitfield, C, H, nears, fars,
     back (one 4-byte device->host copy, as upstream) and M is exact.  Otherwise M
     = mean_count (aligned) and rays overflowing M are dropped; no host sync.
     ``step_counter`` (int32 [2]) receives (total samples, N).
+
+    Preconditions (not checked; ``near_far_from_aabb`` produces them): every direction is a nonzero vector, and
+    ``fars`` is finite wherever ``nears < fars``.  A zero direction or an unbounded far in empty space is a walk that
+    does not end - t stops growing once the step is below half an ulp of t.
     """
     lib = _lib.load()
     rays_o, rays_d = _f(rays_o).view(-1, 3), _f(rays_d).view(-1, 3)
